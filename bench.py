@@ -1,7 +1,15 @@
 """Benchmark: batched NMPC closed-loop steps/s on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N --steps K --warmup W --model quad13 --batch 8192 --precision fp64]
+    python bench.py --full [...]            the full report (below)
+    python bench.py --dump-outputs DIR [...]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run does what the headline figure needs and nothing else: it builds the seeded workload, runs W warm-up
+steps, times K steps once, writes the outputs of the last step if --dump-outputs is given (dump_outputs) and prints
+the line; its roofline credit is the explicit unconstrained solution alone and cpu_baseline is null. --full adds
+what takes runs of its own: --repeats timed regions of K steps (default 10; value = the median region), the CPU
+baseline with the path mix and the flops credit it counts, and the B=1 Python drop-in loop.
 
 Workload (BASELINE.json metric "NMPC steps/sec (batched trajectories), N=20 nx=13 nu=4"):
 the synthetic quad13 OCP (nx=13, nu=4, horizon N=20, no reference counterpart: SURVEY §0),
@@ -25,9 +33,9 @@ Also reported (one JSON line on rank 0):
     the kernel really issues (SQ_INSTS_VALU_FLOPS_FP64 of the committed rocprofv3 PMC pass, idle
     lanes included) / kernel time / peak. traffic = memory-side bytes per step (FETCH_SIZE +
     WRITE_SIZE) from the same PMC pass (profiles/pmc_traffic.json) when one matches, else null.
-  cpu_baseline — oracle/c/riccati_ipm.c's closed loop in mode 1 (the GPU's algorithm: warm-started
+  cpu_baseline (--full) — oracle/c/riccati_ipm.c's closed loop in mode 1 (the GPU's algorithm: warm-started
     fast finish, fp64, OpenMP over instances) on the host cores, rank 0 at N=1 only, over the same
-    instances and steps as the timed GPU run.
+    instances and steps as the timed GPU run (its first CPU_MAX_STEPS steps when the run is longer).
 """
 import argparse
 import json
@@ -42,6 +50,9 @@ sys.path.insert(0, ROOT)
 
 PEAK_TFLOPS = {"fp64": 78.6, "fp32": 157.3}   # MI355X vector = matrix peaks (MI355X_MICROARCH)
 HBM_PEAK_GBS = 8000.0                           # MI355X HBM3E spec peak (MI355X_MICROARCH: 6.29 TB/s measured copy)
+# --full: the CPU baseline follows the GPU run's timed steps up to this many (the default run has 10 x 20); a longer
+# GPU run is compared on its first CPU_MAX_STEPS steps, which keeps the single-core loop to seconds
+CPU_MAX_STEPS = 2000
 
 
 def parse():
@@ -58,12 +69,21 @@ def parse():
                     help="closed_loop (default, the BASELINE metric): the batched closed loop; solve: the "
                          "general batched nmpc_solve on per-instance yref windows (the reference's "
                          "set(k,'yref') / solve() pattern, src/force_model/ocp.py:117-122, controller.py:32)")
-    ap.add_argument("--repeats", type=int, default=10,
-                    help="timed regions of --steps steps each; value = the median region (BASELINE.md: median of >= 10)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--full", action="store_true",
+                    help="the full report: --repeats timed regions (default 10, value = the median region), the CPU "
+                         "baseline of the same algorithm with the roofline credit and path mix it counts, and the B=1 "
+                         "Python drop-in loop. Without it the run sets up, warms up, times --steps steps once and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step to "
+                         "DIR/<name>.npy (float64; see dump_outputs)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; value = the median region (BASELINE.md: median of "
+                         ">= 10). Default: 10 with --full, else 1 (exactly --steps timed steps)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="(--full) time budget of the CPU baseline's sample")
     ap.add_argument("--python-loop-steps", type=int, default=100,
-                    help="steps of the B=1 Python drop-in loop timed for BASELINE config 1 (0: skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="(--full) steps of the B=1 Python drop-in loop timed for BASELINE config 1 (0: skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline and the Python loop")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL over xGMI, the default); gloo only to rehearse several ranks "
                          "on a one-GPU box (ranks then share the visible GPUs round-robin)")
@@ -281,7 +301,7 @@ def workload_label(model, tols, paths, kernel):
     """config.workload: what the timed step runs (`kernel`: the closed-loop kernel launch_info reports),
     with the path mix of the CPU run of the same algorithm over the same steps (None on multi-rank runs,
     which skip the CPU baseline)."""
-    mix = ("path mix not measured in this run (the CPU baseline, which counts it, runs at N=1 only)" if paths is None
+    mix = ("path mix not measured in this run (the CPU baseline counts it: bench.py --full on one GPU)" if paths is None
            else f"of the solves {paths['fast_unconstrained']:.2%} the explicit unconstrained solution, "
                 f"{paths['fast_set']:.2%} warm-started active-set steps on W (incl. the dual active-set fallback), "
                 f"{paths['full']:.3%} the full IPM + exact finish, {paths['failed']:.3%} certified infeasible "
@@ -312,10 +332,37 @@ def emit(line):
     os.write(_JSON_FD if _JSON_FD is not None else 1, (json.dumps(line) + "\n").encode())
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs: all files of a run together stay below this
+
+
+def dump_outputs(dirname, arrays, instance_base, rank, world, seed):
+    """--dump-outputs DIR: `arrays` (name -> per-instance array, first axis = this rank's instances) as float64
+    DIR/<name>.npy, with DIR/instance.npy = the global ids of the rows written. Everything is written while it
+    fits DUMP_BYTES (shared evenly between ranks); beyond that a fixed sample of the instances, drawn from
+    --seed alone, the same rows in every file. Ranks of a multi-GPU run write DIR/<name>.rank<r>.npy. The
+    workload is generated from --seed, so two runs with the same arguments write the same instances."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    B = len(next(iter(arrays.values())))
+    row_bytes = 8 + sum(a[0].nbytes for a in arrays.values())   # + the id column
+    keep = np.arange(B)
+    fit = (DUMP_BYTES // world - 1024 * (len(arrays) + 1)) // row_bytes   # .npy headers: < 1 KiB each
+    if fit < B:
+        keep = np.sort(np.random.default_rng(seed).choice(B, size=int(fit), replace=False))
+    arrays["instance"] = (instance_base + np.arange(B)).astype(np.float64)
+    suffix = "" if world == 1 else f".rank{rank}"
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a[keep])
+
+
 def main():
     args = parse()
     if args.gpus < 1:
         fail(f"--gpus {args.gpus}")
+    if args.steps < 1:
+        fail(f"--steps {args.steps}")
+    if args.repeats is None:   # a plain run times exactly --steps steps
+        args.repeats = 10 if args.full else 1
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args)
     claim_stdout()
@@ -362,10 +409,17 @@ def main():
     regions = np.array(regions)
     st = cl.stats()
     red = np.array([st["cost_sum"], st["aed_sum"], st["failed"], st["instance_steps"]])
-    # CPU baseline and the B=1 Python drop-in loop (rank 0, single-GPU runs only), from the same initial states
+    if args.dump_outputs:
+        # what a caller of the closed loop reads back after its last step: every instance's plant state and its
+        # accumulated [cost sum, AED numerator, failed solves, steps]
+        dump_outputs(args.dump_outputs, {"state": cl.state(), "instance_stats": cl.instance_stats()},
+                     base, rank, world, args.seed)
+    # --full: CPU baseline and the B=1 Python drop-in loop (rank 0, single-GPU runs only), from the same initial
+    # states; the CPU loops are timed on at most CPU_MAX_STEPS of the GPU run's steps
     cpu, flops_cpu, pyloop = None, None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu, flops_cpu = cpu_baseline(model, N, table, offsets_r, x_cpu, args.warmup, args.repeats * args.steps,
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        cpu, flops_cpu = cpu_baseline(model, N, table, offsets_r, x_cpu, args.warmup,
+                                      min(args.repeats * args.steps, CPU_MAX_STEPS),
                                       args.cpu_seconds, "fp64" if lean else args.precision, args.seed)
         if args.python_loop_steps > 0:
             pyloop = python_loop_rate(20, args.python_loop_steps)
@@ -438,7 +492,11 @@ def main():
                          "credit": "FP64 flops per instance-step of the CPU baseline's run of the same algorithm on "
                                    "the same steps (oracle closed loop mode 1, counted per path: explicit solution "
                                    "2 nx per element, active-set steps m^3/3 + 2 m^2 + 2 ne m, full solves F_iter "
-                                   "(SURVEY 8d) per Newton system, plant 2 nx nz) x B / kernel time per step",
+                                   "(SURVEY 8d) per Newton system, plant 2 nx nz) x B / kernel time per step"
+                         if flops_cpu is not None else
+                                   "FP64 flops of one explicit unconstrained solution (2 nx per element) + plant "
+                                   "(2 nx nz) per instance-step x B / kernel time per step; the paths really taken "
+                                   "are counted by the CPU baseline (bench.py --full on one GPU)",
                          "flops_per_instance_step": fl_step, "flops_per_launch": fl_launch, "kernel_ms": kernel_ms,
                          "executed_fp64_flops_per_step": pmc.get("fp64_flops_per_step"),
                          "executed_frac": (pmc["fp64_flops_per_step"] / (kernel_ms * 1e-3) / 1e12 / peak
@@ -503,7 +561,7 @@ def main_solve(args, world, rank, dist, device):
     model = args.model
     N = args.horizon or DEFAULT_N[model]
     B = args.batch
-    table, offsets_r, x_r, _ = rank_workload(model, N, B, world, rank, args.seed)
+    table, offsets_r, x_r, base = rank_workload(model, N, B, world, rank, args.seed)
     x0, Y = first_step_qps(model, N, table, offsets_r, x_r)
     ocp = OCPS[model](N)
     s = AcadosOcpSolver(ocp, batch=B, device=device if world > 1 else 0, precision=args.precision)
@@ -517,7 +575,7 @@ def main_solve(args, world, rank, dist, device):
     # the CPU baseline (after the timed regions: ahead of them the idle GPU's clocks ramp down)
     def cpu_part():
         cpu = None
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             from oracle import cref, models
             ref = cref.RiccatiIpmRef.for_options(models.MODELS[model](N), ocp.solver_options, args.precision)
 
@@ -576,6 +634,10 @@ def main_solve(args, world, rank, dist, device):
               if fast else None)
     status = s.get_batch_int("status")
     iters = s.get_batch_int("qp_iter")
+    if args.dump_outputs:
+        # every timed solve runs the same QPs cold; the synchronous solve after them brings one such result to the host
+        dump_outputs(args.dump_outputs, {"x": s.get_batch("x"), "u": s.get_batch("u"), "status": status,
+                                         "qp_iter": iters}, base, rank, world, args.seed)
     red, regions, kms = reduce_run(dist, np.array([float((status != 0).sum()), float(iters.sum()), float(B)]),
                                    np.array(regions), np.array(kms),
                                    device="cuda" if dist is not None and args.dist_backend == "nccl" else None)

@@ -28,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 
 WORKLOADS = (("quad13", 20, 8192), ("force", 20, 8192), ("jerk", 40, 4096))
-CHECKPOINTS = [3] + [20] * 10          # bench.py: --warmup 3, --repeats 10 x --steps 20
+CHECKPOINTS = [3] + [20] * 10          # bench.py --full: --warmup 3, --repeats 10 x --steps 20
 NSEL = 256
 
 

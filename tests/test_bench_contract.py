@@ -1,6 +1,7 @@
-"""The committed bench line (profiles/r1h_bench_quad13.json, written by bench.py on an MI355X)
-keeps the bench.py JSON contract: required keys, whole-job value consistent with the step time,
-roofline fraction = achieved / peak, and a CPU baseline entry. CPU-only: reads a committed file."""
+"""The committed bench line (profiles/r1h_bench_quad13.json, written by bench.py on an MI355X with
+the CPU baseline, which is now bench.py --full) keeps the bench.py JSON contract: required keys,
+whole-job value consistent with the step time, roofline fraction = achieved / peak, and a CPU
+baseline entry. CPU-only: reads a committed file."""
 import json
 import math
 import pathlib
@@ -49,6 +50,49 @@ def test_cpu_baseline(line):
     c = line["cpu_baseline"]
     assert c["kind"] in ("port", "reference")
     assert c["cores"] >= 1 and c["value"] > 0 and c["sample"]
+
+
+def _npy_bytes(d):
+    return sum(p.stat().st_size for p in d.iterdir())
+
+
+def test_dump_outputs_small_batch_is_written_whole(tmp_path):
+    """--dump-outputs: below the size limit every instance is written, float64, with its global id."""
+    import numpy as np
+
+    import bench
+    x = np.arange(10 * 3, dtype=np.float32).reshape(10, 3)
+    st = np.arange(10, dtype=np.int32)
+    bench.dump_outputs(str(tmp_path), {"x": x, "status": st}, 40, 0, 1, 42)
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["instance.npy", "status.npy", "x.npy"]
+    got = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["x"], x) and np.array_equal(got["status"], st)
+    assert np.array_equal(got["instance"], 40 + np.arange(10))
+
+
+def test_dump_outputs_large_batch_is_a_fixed_sample(tmp_path, monkeypatch):
+    """Above the limit: the files together stay below it, hold the same seeded rows in every file and
+    in every run, and each rank of a multi-GPU run takes its share of the limit under its own names."""
+    import numpy as np
+
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 << 10)
+    x = np.random.default_rng(0).normal(size=(2000, 5, 3))
+    u = x[:, :4, :2].copy()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x, "u": u}, 0, 0, 1, 42)
+    a = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    b = {p.stem: np.load(p) for p in (tmp_path / "b").iterdir()}
+    assert _npy_bytes(tmp_path / "a") <= 64 << 10
+    rows = a["instance"].astype(int)
+    assert 0.9 * (64 << 10) / (8 * (1 + 15 + 8)) < len(rows) < 2000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a["x"], x[rows]) and np.array_equal(a["u"], u[rows])
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    bench.dump_outputs(str(tmp_path / "r"), {"x": x, "u": u}, 2000, 1, 2, 42)
+    assert sorted(p.name for p in (tmp_path / "r").iterdir()) == ["instance.rank1.npy", "u.rank1.npy", "x.rank1.npy"]
+    assert _npy_bytes(tmp_path / "r") <= (64 << 10) // 2
+    assert np.load(tmp_path / "r" / "instance.rank1.npy").min() >= 2000
 
 
 def test_bench_refuses_world_size_mismatch():

@@ -12,7 +12,7 @@ for c in "${CS[@]}"; do
   for r in $(seq ${REPS:-2}); do
     for arm in ${ARMS:-A B}; do
       envs=${!arm}
-      line=$(env $envs timeout -k 10 300 python bench.py $c --no-cpu-baseline --python-loop-steps 0 2>> $OUT/ab_$TAG.err) || { echo "bench failed: $arm $c"; tail -20 $OUT/ab_$TAG.err; exit 1; }
+      line=$(env $envs timeout -k 10 300 python bench.py --full $c --no-cpu-baseline --python-loop-steps 0 2>> $OUT/ab_$TAG.err) || { echo "bench failed: $arm $c"; tail -20 $OUT/ab_$TAG.err; exit 1; }
       python -c "import json,sys; d=json.loads(sys.argv[1]); d['ab_arm']=sys.argv[2]; d['ab_env']=sys.argv[3]; print(json.dumps(d))" "$line" "$arm" "$envs" >> $OUT/ab_$TAG.jsonl
     done
   done
