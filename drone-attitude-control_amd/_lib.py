@@ -95,6 +95,14 @@ SIGNATURES = {
     "nmpc_closed_loop_get_state": (ctypes.c_int, [ctypes.c_void_p, _dp, ctypes.c_size_t]),
     "nmpc_closed_loop_set_outputs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "nmpc_closed_loop_iter_log": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_size_t]),
+    "nmpc_closed_loop_set_history": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "nmpc_closed_loop_history_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]),
+    "nmpc_closed_loop_get_history": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_int, ctypes.c_int, _dp, ctypes.c_size_t]),
+    "nmpc_closed_loop_get_history_int": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
+                                                        ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
+                                                        ctypes.c_size_t]),
+    "nmpc_closed_loop_history_envelope": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_size_t]),
     "nmpc_sim_plant": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                       ctypes.c_double, _dp, _dp, _dp]),
 }
@@ -120,7 +128,13 @@ def load(path=None):
             raise NmpcError(f"HIP library {p} is missing and could not be built: {e}") from e
     lib = ctypes.CDLL(p)
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:
+            # an experimental build selected by NMPC_LIB may predate an entry point (same-box A/B against an
+            # older library): that function is then absent from the handle, and calling it raises AttributeError
+            if p == LIB_PATH:
+                raise NmpcError(f"{p} does not export {name}")
+            continue
         fn.restype = res
         fn.argtypes = args
     if lib.nmpc_abi_version() != NMPC_ABI_VERSION:

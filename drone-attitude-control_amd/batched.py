@@ -178,12 +178,102 @@ class ClosedLoop:
             raise NmpcError(f"nmpc_closed_loop_iter_log: {self.lib.nmpc_last_error(self.solver._h).decode()}")
         return buf & 0xFF, (buf >> 8) & 0xFF, buf >> 16
 
+    def _check(self, rc, fn):
+        if rc != 0:
+            raise NmpcError(f"{fn}: {self.lib.nmpc_last_error(self.solver._h).decode()} (code {rc})")
+
+    def set_history(self, capacity):
+        """Arm the on-device trajectory record (nmpc_closed_loop_set_history) for the next `capacity` closed-loop
+        steps, counted from the loop's current step (the origin); 0 frees it and turns it off. While armed every
+        step of every instance stores the state it started from, the input the plant received and the solve
+        status, on whichever path runs it; later runs stay asynchronous. Steps past the capacity are not stored.
+        Device bytes: capacity * batch * ((nx + nu) * 8 + 4)."""
+        self._check(self.lib.nmpc_closed_loop_set_history(self.solver._h, int(capacity)), "nmpc_closed_loop_set_history")
+
+    def history_info(self):
+        out = (ctypes.c_longlong * 4)()
+        self._check(self.lib.nmpc_closed_loop_history_info(self.solver._h, out, 4), "nmpc_closed_loop_history_info")
+        return {"origin": int(out[0]), "capacity": int(out[1]), "recorded": int(out[2]), "bytes": int(out[3])}
+
+    def _range(self, sel, n, what):
+        """(first, count) of `sel`: None = all n, an int = that one, (a, b) / range / slice with step 1 = [a, b)."""
+        if sel is None:
+            return 0, n
+        if isinstance(sel, (int, np.integer)):
+            return int(sel), 1
+        if isinstance(sel, slice):
+            sel = range(*sel.indices(n))
+        if isinstance(sel, range):
+            if sel.step != 1:
+                raise ValueError(f"{what}: a contiguous range is required")
+            return sel.start, len(sel)
+        a, b = sel
+        return int(a), int(b) - int(a)
+
+    def history(self, instances=None, steps=None):
+        """The recorded closed-loop series of a contiguous instance range and step range (steps relative to the
+        history origin; default: every instance, every recorded step): {"X": [S, n, nx] the state each step started
+        from (Xsim[s] of controller.py's follow_trajectory, plus the acceleration part for jerk), "U": [S, n, nu]
+        the input the plant received, "status": [S, n]}. Waits for the stream; a range beyond the recorded steps
+        raises."""
+        i0, ni = self._range(instances, self.batch, "instances")
+        s0, ns = self._range(steps, self.history_info()["recorded"], "steps")
+        nx, nu, h = self.solver.nx, self.solver.nu, self.solver._h
+        X, U = np.zeros((ns, ni, nx)), np.zeros((ns, ni, nu))
+        st = np.zeros((ns, ni), dtype=np.int32)
+        self._check(self.lib.nmpc_closed_loop_get_history(h, b"x", i0, ni, s0, ns, _lib.dptr(X), X.size),
+                    "nmpc_closed_loop_get_history")
+        self._check(self.lib.nmpc_closed_loop_get_history(h, b"u", i0, ni, s0, ns, _lib.dptr(U), U.size),
+                    "nmpc_closed_loop_get_history")
+        self._check(self.lib.nmpc_closed_loop_get_history_int(h, b"status", i0, ni, s0, ns,
+                                                              st.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), st.size),
+                    "nmpc_closed_loop_get_history_int")
+        return {"X": X, "U": U, "status": st}
+
+    def history_envelope(self, steps=None):
+        """The batch's tracking-error envelope over a recorded step range, reduced on the device: [S, 4] =
+        [sum_b e, max_b e, instances with status != 0, instances recorded] per step, e the step's AED numerator
+        term sum_{i < aed_dims} |reference - state| (their sum over all steps from origin 0 is stats()["aed_sum"])."""
+        s0, ns = self._range(steps, self.history_info()["recorded"], "steps")
+        out = np.zeros((ns, 4))
+        self._check(self.lib.nmpc_closed_loop_history_envelope(self.solver._h, s0, ns, _lib.dptr(out), out.size),
+                    "nmpc_closed_loop_history_envelope")
+        return out
+
     def state(self):
         out = np.zeros((self.batch, self.solver.nx))
         rc = self.lib.nmpc_closed_loop_get_state(self.solver._h, _lib.dptr(out), out.size)
         if rc != 0:
             raise NmpcError(f"nmpc_closed_loop_get_state: {self.lib.nmpc_last_error(self.solver._h).decode()}")
         return out
+
+
+def reference_outputs(model, X, U, x_last):
+    """The reference driver's outputs for one instance from its recorded series (ClosedLoop.history): follow_trajectory
+    in the reference's src/*/controller.py returns (cost, Xsim, a, U_opt_plant); this returns
+    (Xsim [S+1, 4], a [S, 2], U_opt_plant [S, 2]) — pure numpy, the converters of controllers.py.
+    X [S, nx]: the state each step started from, U [S, nu]: the input the plant received, x_last: the state after
+    the last step (ClosedLoop.state() row; its first 4 components are used).
+    force: a = U / MASS, U_opt_plant[t] = force_convert(U[t]); jerk: (u_tmp, a[t]) = jerk_convert(U[t], X[t, 4:6]),
+    U_opt_plant[t] = u_tmp[-1]. quad13 has no plant converter: ValueError."""
+    from .controllers import force_convert, jerk_convert
+    if model not in ("force", "jerk"):
+        raise ValueError(f"reference_outputs: model '{model}' has no plant converter (force / jerk only)")
+    X, U = np.asarray(X, dtype=np.float64), np.asarray(U, dtype=np.float64)
+    nx = 4 if model == "force" else 6
+    if X.ndim != 2 or U.ndim != 2 or X.shape[1] != nx or U.shape != (X.shape[0], 2):
+        raise ValueError(f"reference_outputs: X must be [S, {nx}] and U [S, 2]")
+    S = X.shape[0]
+    Xsim = np.vstack([X[:, :4], np.asarray(x_last, dtype=np.float64).reshape(-1)[:4]])
+    a, Up = np.zeros((S, 2)), np.zeros((S, 2))
+    for t in range(S):
+        if model == "force":
+            a[t] = U[t] / dd.MASS
+            Up[t] = force_convert(U[t])
+        else:
+            u_tmp, a[t] = jerk_convert(U[t], X[t, 4:6])
+            Up[t] = u_tmp[-1]
+    return Xsim, a, Up
 
 
 def flops_per_iter(nx, nu, N):

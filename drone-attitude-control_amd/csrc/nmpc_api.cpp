@@ -274,6 +274,11 @@ struct nmpc_solver {
     int *d_offsets = nullptr;
     double *d_acc = nullptr, *d_noise = nullptr;
     int cl_step = 0, cl_last_launches = 0, cl_last_steps = 0;
+    // closed-loop history (nmpc_closed_loop_set_history; null: off): planes [hist_cap][B][nx | nu | 1], rows by
+    // closed-loop step - hist_origin
+    double *d_hist_x = nullptr, *d_hist_u = nullptr;
+    int *d_hist_s = nullptr;
+    int hist_origin = 0, hist_cap = 0;
     double *d_fnoise = nullptr;   // fused closed loop: noise draws of a launch's steps [B][64]
     int *d_iter_log = nullptr;    // fused closed loop, env NMPC_ITER_LOG: per-step finish steps | IPM iterations << 8 | status << 16 [64][B]
     int iter_log_steps = 0;       // steps in the log (the last fused launch; the lean loop: the last run)
@@ -538,7 +543,7 @@ void free_all(nmpc_solver *h)
                     (void *)h->d_istep, (void *)h->d_park, (void *)h->d_flags, h->d_clf_scratch, (void *)h->d_clw,
                     (void *)h->d_fin_f, (void *)h->d_fin_i, (void *)h->d_z0, (void *)h->d_sf, (void *)h->d_f64,
                     (void *)h->d_f64i, (void *)h->d_sfl, h->d_sf_scratch, (void *)h->d_sfcyc, (void *)h->d_clf_check, (void *)h->d_imap,
-                    (void *)h->d_gorder})
+                    (void *)h->d_gorder, (void *)h->d_hist_x, (void *)h->d_hist_u, (void *)h->d_hist_s})
         if (p) hipFree(p);
     if (h->h_sfpark) hipHostFree(h->h_sfpark);
     if (h->ev_fb) hipEventDestroy(h->ev_fb);
@@ -612,6 +617,7 @@ int launch_cond(nmpc_solver *h, hipEvent_t e0, hipEvent_t e1)
 
 template <typename T>
 nmpc::ClParams<T> cl_params(nmpc_solver *h);
+nmpc::HistParams hist_params(const nmpc_solver *h);
 
 constexpr int CL_FUSED_CHUNK = 64;   // closed-loop steps per fused solve launch
 constexpr int CLF_CHUNK = 64;        // closed-loop steps per lean-loop launch (bounded noise / log buffers)
@@ -665,6 +671,7 @@ int launch(nmpc_solver *h, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, int
     }
     if (cl_steps > 0) {
         p.cl = cl_params<T>(h);
+        p.hist = hist_params(h);
         p.cl_noise = h->d_fnoise;
         // env NMPC_ITER_LOG: the fused launch's step record. The list mode (the lean loop's fallback)
         // neither writes nor resizes it: the lean loop's own log (clf_run) stays as that run left it
@@ -1583,6 +1590,12 @@ nmpc::ClParams<T> cl_params(nmpc_solver *h)
     return p;
 }
 
+// the armed closed-loop history (x null: off)
+nmpc::HistParams hist_params(const nmpc_solver *h)
+{
+    return nmpc::HistParams{h->d_hist_x, h->d_hist_u, h->d_hist_s, h->hist_origin, h->hist_cap};
+}
+
 // fused closed loop: the kernel families that run the steps inside the solve kernel
 bool cl_fused(nmpc_solver *h)
 {
@@ -1613,7 +1626,7 @@ int cl_step_enqueue(nmpc_solver *h, int launch_idx)
     if (e != hipSuccess) return hip_fail(h, e, "closed-loop prepare");
     const int r = launch<T>(h, h->cl_events[2 * launch_idx], h->cl_events[2 * launch_idx + 1]);
     if (r < 0) return r;
-    e = nmpc::cl_advance_launch<T>(p, h->stream);
+    e = nmpc::cl_advance_launch<T>(p, hist_params(h), h->stream);
     if (e != hipSuccess) return hip_fail(h, e, "closed-loop advance");
     h->cl_step++;
     return 0;
@@ -2314,6 +2327,11 @@ nmpc::ClFastParams<T> clf_params(nmpc_solver *h, int target, int step0, int nois
     // the rare path's W column cache in the workgroup's LDS (the shapes with sets of up to 16)
     const char *wce = std::getenv("NMPC_CLF_WCACHE");
     p.wcache = (wce && wce[0] == '0') ? 0 : 1;
+    p.hist_x = h->d_hist_x;   // set: cl_fast_launch takes the recording instantiation
+    p.hist_u = h->d_hist_u;
+    p.hist_status = h->d_hist_s;
+    p.hist_origin = h->hist_origin;
+    p.hist_cap = h->hist_cap;
     return p;
 }
 
@@ -2547,6 +2565,44 @@ int clf_resync(nmpc_solver *h)
     return e == hipSuccess ? 0 : hip_fail(h, e, "lean closed loop resync");
 }
 
+// closed-loop history off: the planes freed (the stream must have drained). A failed free is reported.
+int hist_release(nmpc_solver *h)
+{
+    hipError_t e = hipSuccess;
+    for (void **p : {(void **)&h->d_hist_x, (void **)&h->d_hist_u, (void **)&h->d_hist_s}) {
+        if (*p) {
+            const hipError_t ef = hipFree(*p);
+            if (e == hipSuccess) e = ef;
+        }
+        *p = nullptr;
+    }
+    h->hist_origin = h->hist_cap = 0;
+    return e == hipSuccess ? 0 : hip_fail(h, e, "closed-loop history free");
+}
+
+int hist_recorded(const nmpc_solver *h)
+{
+    return h->d_hist_x ? std::max(0, std::min(h->hist_cap, h->cl_step - h->hist_origin)) : 0;
+}
+
+// a (step range x instance range) block of one history plane ([cap][B][w] elements of `es` bytes) to the host
+int hist_download(nmpc_solver *h, const char *fn, const void *plane, int w, size_t es, int inst0, int ninst, int step0,
+                  int nsteps, void *out, size_t count)
+{
+    if (!h->d_hist_x) return h->fail(NMPC_ESTATE, std::string(fn) + ": history is off (nmpc_closed_loop_set_history)");
+    if (inst0 < 0 || ninst < 1 || inst0 > h->batch - ninst || step0 < 0 || nsteps < 1 || step0 > hist_recorded(h) - nsteps)
+        return h->fail(NMPC_EINVAL, std::string(fn) + ": range outside [0, recorded) x [0, batch)");
+    if (count != (size_t)nsteps * ninst * w) return h->fail(NMPC_EINVAL, std::string(fn) + ": needs nsteps*ninst*width values");
+    hipError_t e = hipSetDevice(h->device);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return hip_fail(h, e, fn);
+    const size_t pitch = (size_t)h->batch * w * es, width = (size_t)ninst * w * es;
+    const char *src = (const char *)plane + (size_t)step0 * pitch + (size_t)inst0 * w * es;
+    if ((e = hipMemcpy2D(out, width, src, pitch, width, (size_t)nsteps, hipMemcpyDeviceToHost)) != hipSuccess)
+        return hip_fail(h, e, fn);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2571,6 +2627,12 @@ int nmpc_closed_loop_init(nmpc_solver *h, const nmpc_closed_loop_desc *d)
     for (int b = 0; b < h->batch; b++)
         if (d->offsets[b] < 0) return h->fail(NMPC_EINVAL, "nmpc_closed_loop_init: negative offset");
     hipSetDevice(h->device);
+    if (h->d_hist_x) {   // a new loop: its history starts off
+        hipError_t eh = hipStreamSynchronize(h->stream);
+        if (eh != hipSuccess) return hip_fail(h, eh, "nmpc_closed_loop_init");
+        const int r = hist_release(h);
+        if (r < 0) return r;
+    }
     const bool f64 = h->precision == NMPC_FP64;
     const size_t es = h->esz();
     for (void **p : {&h->d_table, &h->d_state, &h->d_plant, &h->d_wcl, (void **)&h->d_offsets, (void **)&h->d_acc,
@@ -2808,6 +2870,111 @@ int nmpc_closed_loop_get_state(nmpc_solver *h, double *out, size_t count)
         for (size_t i = 0; i < count; i++) out[i] = t[i];
     }
     if (e != hipSuccess) return hip_fail(h, e, "nmpc_closed_loop_get_state");
+    return 0;
+}
+
+int nmpc_closed_loop_set_history(nmpc_solver *h, int capacity_steps)
+{
+    if (!h) return NMPC_EINVAL;
+    if (!h->cl_ready) return h->fail(NMPC_ESTATE, "nmpc_closed_loop_set_history: call nmpc_closed_loop_init first");
+    if (capacity_steps < 0) return h->fail(NMPC_EINVAL, "nmpc_closed_loop_set_history: capacity < 0");
+    hipError_t e = hipSetDevice(h->device);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // no enqueued step still writes the old planes
+    if (e != hipSuccess) return hip_fail(h, e, "nmpc_closed_loop_set_history");
+    int r = hist_release(h);
+    if (r < 0 || capacity_steps == 0) return r;
+    const size_t rows = (size_t)capacity_steps * h->batch;
+    const size_t nxe = rows * h->nx, nue = rows * h->nu;
+    hipError_t ex = hipMalloc((void **)&h->d_hist_x, nxe * sizeof(double));
+    hipError_t eu = ex == hipSuccess ? hipMalloc((void **)&h->d_hist_u, nue * sizeof(double)) : ex;
+    hipError_t es = eu == hipSuccess ? hipMalloc((void **)&h->d_hist_s, rows * sizeof(int)) : eu;
+    if (es != hipSuccess) {
+        if (ex != hipSuccess) h->d_hist_x = nullptr;
+        if (eu != hipSuccess) h->d_hist_u = nullptr;
+        h->d_hist_s = nullptr;
+        (void)hipGetLastError();   // the failed allocation is reported here, not by a later launch's check
+        if ((r = hist_release(h)) < 0) return r;
+        return h->fail(NMPC_ENOMEM, std::string("nmpc_closed_loop_set_history: device allocation failed: ") + hipGetErrorString(es));
+    }
+    e = nmpc::hist_fill_launch(h->d_hist_x, h->d_hist_u, h->d_hist_s, nxe, nue, rows, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        (void)hist_release(h);
+        return hip_fail(h, e, "nmpc_closed_loop_set_history: prefill");
+    }
+    h->hist_origin = h->cl_step;
+    h->hist_cap = capacity_steps;
+    return 0;
+}
+
+int nmpc_closed_loop_history_info(nmpc_solver *h, long long *out, int n)
+{
+    if (!h || !out) return NMPC_EINVAL;
+    if (!h->cl_ready) return h->fail(NMPC_ESTATE, "nmpc_closed_loop_history_info: closed loop not initialised");
+    const bool on = h->d_hist_x != nullptr;
+    const long long v[4] = {on ? h->hist_origin : 0, on ? h->hist_cap : 0, hist_recorded(h),
+                            on ? (long long)h->hist_cap * h->batch * ((long long)(h->nx + h->nu) * 8 + 4) : 0};
+    for (int i = 0; i < n && i < 4; i++) out[i] = v[i];
+    return 0;
+}
+
+int nmpc_closed_loop_get_history(nmpc_solver *h, const char *field, int inst0, int ninst, int step0, int nsteps,
+                                 double *out, size_t count)
+{
+    if (!h || !field || !out) return NMPC_EINVAL;
+    const bool fx = std::strcmp(field, "x") == 0;
+    if (!fx && std::strcmp(field, "u") != 0)
+        return h->fail(NMPC_EINVAL, std::string("nmpc_closed_loop_get_history: unknown field '") + field + "'");
+    return hist_download(h, "nmpc_closed_loop_get_history", fx ? h->d_hist_x : h->d_hist_u, fx ? h->nx : h->nu, sizeof(double),
+                         inst0, ninst, step0, nsteps, out, count);
+}
+
+int nmpc_closed_loop_get_history_int(nmpc_solver *h, const char *field, int inst0, int ninst, int step0, int nsteps,
+                                     int32_t *out, size_t count)
+{
+    if (!h || !field || !out) return NMPC_EINVAL;
+    if (std::strcmp(field, "status") != 0)
+        return h->fail(NMPC_EINVAL, std::string("nmpc_closed_loop_get_history_int: unknown field '") + field + "'");
+    return hist_download(h, "nmpc_closed_loop_get_history_int", h->d_hist_s, 1, sizeof(int32_t), inst0, ninst, step0, nsteps,
+                         out, count);
+}
+
+int nmpc_closed_loop_history_envelope(nmpc_solver *h, int step0, int nsteps, double *out, size_t count)
+{
+    if (!h || !out) return NMPC_EINVAL;
+    if (!h->d_hist_x) return h->fail(NMPC_ESTATE, "nmpc_closed_loop_history_envelope: history is off (nmpc_closed_loop_set_history)");
+    if (step0 < 0 || nsteps < 1 || step0 > hist_recorded(h) - nsteps)
+        return h->fail(NMPC_EINVAL, "nmpc_closed_loop_history_envelope: step range outside [0, recorded)");
+    if (count != (size_t)nsteps * 4) return h->fail(NMPC_EINVAL, "nmpc_closed_loop_history_envelope: needs nsteps*4 values");
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return hip_fail(h, e, "nmpc_closed_loop_history_envelope");
+    double *d_out = nullptr;
+    if ((e = hipMalloc((void **)&d_out, count * sizeof(double))) != hipSuccess) {
+        (void)hipGetLastError();
+        return h->fail(NMPC_ENOMEM, "nmpc_closed_loop_history_envelope: device allocation failed");
+    }
+    nmpc::HistEnvParams p{};
+    p.B = h->batch;
+    p.nx = h->nx;
+    p.aed_dims = h->cl.aed_dims;
+    p.period = h->cl.ref_period;
+    p.table_cols = h->cl.ref_cols;
+    p.origin = h->hist_origin;
+    p.row0 = step0;
+    p.nrows = nsteps;
+    p.f64 = h->precision == NMPC_FP64;
+    p.table = h->d_table;
+    p.offset = h->d_offsets;
+    p.hist_x = h->d_hist_x;
+    p.hist_status = h->d_hist_s;
+    p.out = d_out;
+    // in stream order behind the enqueued steps; the copy waits for the kernel
+    e = nmpc::hist_envelope_launch(p, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, count * sizeof(double), hipMemcpyDeviceToHost);
+    const hipError_t ef = hipFree(d_out);
+    if (e == hipSuccess) e = ef;
+    if (e != hipSuccess) return hip_fail(h, e, "nmpc_closed_loop_history_envelope");
     return 0;
 }
 

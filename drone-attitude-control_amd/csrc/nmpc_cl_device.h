@@ -70,7 +70,7 @@ __device__ __forceinline__ void crazyflie_rhs(const double x[4], double st, doub
 // NXC > 0: the controller-model plant at that compile-time size (registers, no scratch arrays);
 // NXC = 0: runtime sizes. Both keep the arithmetic order of cl_advance_kernel.
 template <typename T, int NXC = 0, int NUC = 0>
-__device__ void cl_advance_instance(const ClParams<T> &p, int b, int step, int status)
+__device__ void cl_advance_instance(const ClParams<T> &p, int b, int step, int status, const HistParams &hs)
 {
     // plants a model of this size can drive (nmpc_closed_loop_init checks the pairing)
     constexpr bool PL1 = NXC == 0 || (NXC == 4 && NUC == 2), PL2 = NXC == 0 || (NXC == 6 && NUC == 2);
@@ -86,6 +86,15 @@ __device__ void cl_advance_instance(const ClParams<T> &p, int b, int step, int s
         cost += (double)p.wcl[i] * e * e;
     }
     for (int i = 0; i < p.aed_dims; i++) aed += fabs((double)xref[i] - (double)st[i]);
+    if (hs.x) {   // history: the state the step started from, the plant's input, the status (one writer per row)
+        const int row = hist_row(step, hs.origin, hs.cap);
+        if (row >= 0) {
+            const size_t o = (size_t)row * p.B + b;
+            for (int i = 0; i < nx; i++) hs.x[o * nx + i] = (double)st[i];
+            for (int j = 0; j < nu; j++) hs.u[o * nu + j] = (double)u0[j];
+            hs.status[o] = status;
+        }
+    }
     const double w = noise_draw(p.seed, p.inst_base, p.noise_std, p.noise_table, p.noise_len, b, step);
     if (p.plant == 0) {
         // controller's own discrete model
@@ -166,8 +175,11 @@ namespace nmpc {
 // cl_noise_launch (no Box-Muller in the solve kernels). The group's solve outputs must be visible
 // (the caller fences); every lane reads the old state before any lane stores a new row (each
 // store depends on all of its lane's loads and the wavefront executes in lockstep).
-template <typename T, int NX, int NU>
-__device__ __forceinline__ void cl_advance_group(const ClParams<T> &p, int b, int step, int status, int r, double w)
+// REC: the recording instantiation (closed-loop history armed; the solve kernels' launch glue picks it when
+// hs.x is set, so the default kernels carry no trace of it).
+template <typename T, int NX, int NU, bool REC = false>
+__device__ __forceinline__ void cl_advance_group(const ClParams<T> &p, int b, int step, int status, int r, double w,
+                                                 const HistParams &hs)
 {
     constexpr bool PL1 = NX == 4 && NU == 2, PL2 = NX == 6 && NU == 2;
     T *st = p.state + (size_t)b * NX;
@@ -182,6 +194,17 @@ __device__ __forceinline__ void cl_advance_group(const ClParams<T> &p, int b, in
             cost += (double)p.wcl[i] * e * e;
         }
         for (int i = 0; i < p.aed_dims; i++) aed += fabs((double)xref[i] - (double)st[i]);
+    }
+    if constexpr (REC) {   // history (as cl_advance_instance): lane r < NX stores x_r, lane 0 the inputs and the status
+        const int row = hist_row(step, hs.origin, hs.cap);
+        if (row >= 0) {
+            const size_t o = (size_t)row * p.B + b;
+            if (r < NX) hs.x[o * NX + r] = (double)st[r];
+            if (r == 0) {
+                for (int j = 0; j < NU; j++) hs.u[o * NU + j] = (double)u0[j];
+                hs.status[o] = status;
+            }
+        }
     }
     if (p.plant == 0) {
         if (r < NX) {

@@ -1428,7 +1428,10 @@ __device__ int slow_step(const ClFastParams<T> &p, LdsT &L, const SlotView<EPL> 
 // and the lockstep kernel's rare path): record load, per step the warm-start shift, the explicit form
 // (explicit_form(z, vt): z = v_t + T_x x at the lane's slots, x in L.xs), the bound test, slow_step when
 // needed, flags, u0, cost / AED, the outputs at the last step, the plant; write-back (or park).
-template <typename T, int NX, int NU, int EPL, int WSM, class SP, class LdsT, class ExplicitF>
+// REC: the recording instantiation (closed-loop history armed): each step also stores the state it started from,
+// the plant's input and the status to p.hist_* (row step - hist_origin; a parked step stores nothing — the
+// list-mode solve that finishes it does). The default instantiation never touches p.hist_*.
+template <typename T, int NX, int NU, int EPL, int WSM, class SP, bool REC, class LdsT, class ExplicitF>
 __device__ __forceinline__ void run_instance(const ClFastParams<T> &p, LdsT &L, const SlotView<EPL> sv, int lane,
                                              const double *abl, const double *cl, int inst, ExplicitF &&explicit_form,
                                              WCacheOf<WSM, EPL> *wc = nullptr)
@@ -1578,6 +1581,21 @@ __device__ __forceinline__ void run_instance(const ClFastParams<T> &p, LdsT &L, 
         if (p.traj_out && step + 1 == p.target) write_outputs<T, NX, NU, EPL>(p, L, sv, lane, inst, t, status, m_acc, z);
         CLF_TADD(L, 7, to0);
         CLF_T(tl0);
+        if constexpr (REC) {   // history row of this step (wave-uniform row; lanes < NX hold x, u0 / status uniform)
+            const int row = hist_row(step, p.hist_origin, p.hist_cap);
+            if (row >= 0) {
+                const size_t o = (size_t)row * p.B + inst;
+                if (lane < NX) p.hist_x[o * NX + lane] = (double)(T)xl;
+                if (lane < NU) {
+                    double uv = u0[0];
+#pragma unroll
+                    for (int i = 1; i < NU; i++)
+                        if (lane == i) uv = u0[i];
+                    p.hist_u[o * NU + lane] = uv;
+                }
+                if (lane == 0) p.hist_status[o] = status;
+            }
+        }
         // ---- plant step + noise
         xl = plant_step<T, NX, NU, SP>(p, abl, cl, L.xs, xl, u0, w, lane);
         CLF_TADD(L, 8, tl0);
@@ -1701,7 +1719,7 @@ __device__ __forceinline__ void gen_noise(const ClFastParams<T> &p, int wg_lo, i
 
 // WPB wavefronts per workgroup (the slot tables in LDS are shared by them), MW the occupancy target
 // (waves per SIMD; 0: none)
-template <typename T, int NX, int NU, int EPL, int WSM, int WPB, int MW, class SP, bool WL = false, bool SW2 = false>
+template <typename T, int NX, int NU, int EPL, int WSM, int WPB, int MW, class SP, bool WL = false, bool SW2 = false, bool REC = false>
 __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(MW > 0 ? MW : 1, 8))) void cl_fast_kernel(ClFastParams<T> p)
 {
     if (p.run_if && __builtin_amdgcn_readfirstlane(*p.run_if) == 0) return;   // an empty asynchronous round
@@ -1803,7 +1821,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(MW > 0
         const int pos = wg_lo + (ordered ? (int)ord[next] : next);
         const int inst = p.claim_global ? (p.gorder ? p.gorder[pos] : pos) : (p.inst_map ? p.inst_map[pos] : pos);
         // explicit unconstrained solution at the lane's slots: T_x pairs from LDS against x pairs broadcast
-        run_instance<T, NX, NU, EPL, WSM, SP>(p, L, sv, lane, abl, cl, inst, [&](T(&z)[EPL], const T(&vt)[EPL]) {
+        run_instance<T, NX, NU, EPL, WSM, SP, REC>(p, L, sv, lane, abl, cl, inst, [&](T(&z)[EPL], const T(&vt)[EPL]) {
             T z1[EPL];
 #pragma unroll
             for (int j = 0; j < EPL; j++) {
@@ -2045,7 +2063,7 @@ __global__ __launch_bounds__(64 * WPB) void fin64_kernel(ClFastParams<double> p)
 // Same decisions, thresholds and outputs as cl_fast_kernel (oracle/c/riccati_ipm.c mode 1); only the
 // summation order of the explicit form and the plant differs (rounding).
 
-template <typename T, int NX, int NU, int EPL, int WSM, int WPB, int MW, class SP>
+template <typename T, int NX, int NU, int EPL, int WSM, int WPB, int MW, class SP, bool REC = false>
 __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(MW > 0 ? MW : 1, MW > 0 ? MW : 8))) void cl_lock_kernel(ClFastParams<T> p)
 {
     if (p.run_if && __builtin_amdgcn_readfirstlane(*p.run_if) == 0) return;   // an empty asynchronous round
@@ -2378,6 +2396,20 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(MW > 0
                     }
                 }
             }
+            if constexpr (REC) {   // history rows of the advancing instances (a demoted one's step is recorded by
+                                   // whoever finishes it): x_c on lanes 16 ti + n of block 0, u0 on those with ti < NU
+                const int row = hist_row(step, p.hist_origin, p.hist_cap);
+                if (adv && tb == 0 && row >= 0) {
+                    const size_t o = (size_t)row * p.B + inst;
+#pragma unroll
+                    for (int kc = 0; kc < KC; kc++) {
+                        const int c = 4 * kc + ti;
+                        if (c < NX) p.hist_x[o * NX + c] = xr[kc];
+                    }
+                    if (ti < NU) p.hist_u[o * NU + ti] = u0v;
+                    if (ti == 0) p.hist_status[o] = 0;
+                }
+            }
             if constexpr (NX == 6 && NU == 2) {
                 if (p.plant == 2) {
                     // ---- the jerk converter plant (plant_step's arithmetic, src/plant.py): every lane of
@@ -2493,7 +2525,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(MW > 0
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         // explicit form of one instance on the same MFMA tiles: all four B columns the instance's x (L.xs),
         // the n = 0 lanes' results staged to slot order
-        run_instance<T, NX, NU, EPL, WSM, SP>(p, L, sv, lane, abl, cl, inst, [&](T(&z)[EPL], const T(&vt)[EPL]) {
+        run_instance<T, NX, NU, EPL, WSM, SP, REC>(p, L, sv, lane, abl, cl, inst, [&](T(&z)[EPL], const T(&vt)[EPL]) {
             T zq[NT];
 #pragma unroll
             for (int q = 0; q < NT; q++) zq[q] = T(0);
@@ -2541,12 +2573,15 @@ template <typename T_, int NX_, int NU_, int EPL_, int WSM_, int WPB_, int MW_, 
 struct Variant {
     static constexpr int WPB = WPB_;
     static constexpr auto kernel() { return clf::cl_fast_kernel<T_, NX_, NU_, EPL_, WSM_, WPB_, MW_, SP_, WL_, SW2_>; }
+    // the recording instantiation (closed-loop history armed)
+    static constexpr auto kernel_rec() { return clf::cl_fast_kernel<T_, NX_, NU_, EPL_, WSM_, WPB_, MW_, SP_, WL_, SW2_, true>; }
 };
 // the lockstep kernel (four instances per wavefront, MFMA explicit form and plant)
 template <typename T_, int NX_, int NU_, int EPL_, int WSM_, int WPB_, int MW_, class SP_>
 struct LockVariant {
     static constexpr int WPB = WPB_;
     static constexpr auto kernel() { return clf::cl_lock_kernel<T_, NX_, NU_, EPL_, WSM_, WPB_, MW_, SP_>; }
+    static constexpr auto kernel_rec() { return clf::cl_lock_kernel<T_, NX_, NU_, EPL_, WSM_, WPB_, MW_, SP_, true>; }
 };
 
 // whether the shape has a lockstep kernel (quad13; jerk, whose plant may be its converter and whose cost may
@@ -2648,7 +2683,9 @@ hipError_t cl_fast_launch(int nx, int nu, int sid, int kind, const ClFastParams<
         // the lockstep kernel: four instances per wavefront
         const int wv = kind == CLF_LOCK ? (waves + 3) / 4 : waves;
         const int blocks = std::max(1, std::min((wv + V::WPB - 1) / V::WPB, resident));
-        NMPC_LAUNCH(V::kernel(), dim3(blocks), dim3(64 * V::WPB), 0, s, p);
+        // history armed: the recording instantiation (same launch shape; the default kernel's code is untouched)
+        if (p.hist_x) NMPC_LAUNCH(V::kernel_rec(), dim3(blocks), dim3(64 * V::WPB), 0, s, p);
+        else NMPC_LAUNCH(V::kernel(), dim3(blocks), dim3(64 * V::WPB), 0, s, p);
     });
     return ok ? hipGetLastError() : hipErrorInvalidValue;
 }

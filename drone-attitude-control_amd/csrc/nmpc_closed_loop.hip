@@ -46,20 +46,20 @@ __global__ __launch_bounds__(256) void cl_prepare_kernel(ClParams<T> p)
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void cl_advance_kernel(ClParams<T> p)
+__global__ __launch_bounds__(256) void cl_advance_kernel(ClParams<T> p, HistParams hs)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= p.B) return;
-    cl_advance_instance<T>(p, b, p.step, p.status[b]);
+    cl_advance_instance<T>(p, b, p.step, p.status[b], hs);
 }
 
 // the controller-model plant at a compile-time size (state / input in registers)
 template <typename T, int NX, int NU>
-__global__ __launch_bounds__(256) void cl_model_advance_kernel(ClParams<T> p)
+__global__ __launch_bounds__(256) void cl_model_advance_kernel(ClParams<T> p, HistParams hs)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= p.B) return;
-    cl_advance_instance<T, NX, NU>(p, b, p.step, p.status[b]);
+    cl_advance_instance<T, NX, NU>(p, b, p.step, p.status[b], hs);
 }
 
 template <typename T>
@@ -94,20 +94,95 @@ hipError_t cl_prepare_launch(const ClParams<T> &p, hipStream_t s)
 }
 
 template <typename T>
-hipError_t cl_advance_launch(const ClParams<T> &p, hipStream_t s)
+hipError_t cl_advance_launch(const ClParams<T> &p, const HistParams &hs, hipStream_t s)
 {
     if (p.plant == 0 && p.nx == 13 && p.nu == 4) {   // quad13 (the headline model)
-        NMPC_LAUNCH((cl_model_advance_kernel<T, 13, 4>), dim3((p.B + 255) / 256), dim3(256), 0, s, p);
+        NMPC_LAUNCH((cl_model_advance_kernel<T, 13, 4>), dim3((p.B + 255) / 256), dim3(256), 0, s, p, hs);
         return hipGetLastError();
     }
-    NMPC_LAUNCH(cl_advance_kernel<T>, dim3((p.B + 255) / 256), dim3(256), 0, s, p);
+    NMPC_LAUNCH(cl_advance_kernel<T>, dim3((p.B + 255) / 256), dim3(256), 0, s, p, hs);
+    return hipGetLastError();
+}
+
+// ---- closed-loop history (nmpc_closed_loop_set_history): prefill and the batch envelope
+
+__global__ __launch_bounds__(256) void hist_fill_kernel(double *hx, double *hu, int *hs, size_t nxe, size_t nue, size_t nse)
+{
+    const double nan = __builtin_nan("");
+    const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    for (size_t i = t0; i < nxe; i += stride) hx[i] = nan;
+    for (size_t i = t0; i < nue; i += stride) hu[i] = nan;
+    for (size_t i = t0; i < nse; i += stride) hs[i] = -1;
+}
+
+hipError_t hist_fill_launch(double *hx, double *hu, int *hs, size_t nxe, size_t nue, size_t nse, hipStream_t s)
+{
+    const int blocks = (int)std::max<size_t>(1, std::min<size_t>((nxe + 255) / 256, 8192));
+    NMPC_LAUNCH(hist_fill_kernel, dim3(blocks), dim3(256), 0, s, hx, hu, hs, nxe, nue, nse);
+    return hipGetLastError();
+}
+
+// One workgroup per history row (closed-loop step): thread t takes instances t, t + 256, ... in order, then the
+// wavefront's 64 partials are combined by a cross-lane butterfly and the four wavefronts' through LDS in wavefront
+// order — a fixed reduction tree, no atomics: the same bits on every call. Rows never written (status -1) are skipped.
+template <typename T>
+__global__ __launch_bounds__(256) void hist_envelope_kernel(HistEnvParams p)
+{
+    __shared__ double red[4][4];
+    const int row = p.row0 + (int)blockIdx.x, step = p.origin + row;
+    const T *table = (const T *)p.table;
+    const double *hx = p.hist_x + (size_t)row * p.B * p.nx;
+    const int *hs = p.hist_status + (size_t)row * p.B;
+    double sum = 0.0, mx = 0.0, nfail = 0.0, nrec = 0.0;
+    for (int b = threadIdx.x; b < p.B; b += 256) {
+        const int st = hs[b];
+        if (st < 0) continue;
+        const unsigned per = (unsigned)p.period;
+        const int t = (int)(((unsigned)p.offset[b] % per + (unsigned)step % per) % per);
+        const T *xref = table + (size_t)t * p.table_cols;
+        double e = 0.0;
+        for (int i = 0; i < p.aed_dims; i++) e += fabs((double)xref[i] - hx[(size_t)b * p.nx + i]);
+        sum += e;
+        mx = fmax(mx, e);
+        nfail += st != 0 ? 1.0 : 0.0;
+        nrec += 1.0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        sum += __shfl_xor(sum, o);
+        mx = fmax(mx, __shfl_xor(mx, o));
+        nfail += __shfl_xor(nfail, o);
+        nrec += __shfl_xor(nrec, o);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        red[wave][0] = sum;
+        red[wave][1] = mx;
+        red[wave][2] = nfail;
+        red[wave][3] = nrec;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double *o = p.out + (size_t)blockIdx.x * 4;
+        o[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+        o[1] = fmax(fmax(red[0][1], red[1][1]), fmax(red[2][1], red[3][1]));
+        o[2] = ((red[0][2] + red[1][2]) + red[2][2]) + red[3][2];
+        o[3] = ((red[0][3] + red[1][3]) + red[2][3]) + red[3][3];
+    }
+}
+
+hipError_t hist_envelope_launch(const HistEnvParams &p, hipStream_t s)
+{
+    if (p.nrows < 1 || p.B < 1) return hipErrorInvalidValue;
+    if (p.f64) NMPC_LAUNCH(hist_envelope_kernel<double>, dim3(p.nrows), dim3(256), 0, s, p);
+    else NMPC_LAUNCH(hist_envelope_kernel<float>, dim3(p.nrows), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
 template hipError_t cl_prepare_launch<double>(const ClParams<double> &, hipStream_t);
 template hipError_t cl_prepare_launch<float>(const ClParams<float> &, hipStream_t);
-template hipError_t cl_advance_launch<double>(const ClParams<double> &, hipStream_t);
-template hipError_t cl_advance_launch<float>(const ClParams<float> &, hipStream_t);
+template hipError_t cl_advance_launch<double>(const ClParams<double> &, const HistParams &, hipStream_t);
+template hipError_t cl_advance_launch<float>(const ClParams<float> &, const HistParams &, hipStream_t);
 template hipError_t cl_noise_launch<double>(const ClParams<double> &, int, int, double *, hipStream_t, int *);
 template hipError_t cl_noise_launch<float>(const ClParams<float> &, int, int, double *, hipStream_t, int *);
 

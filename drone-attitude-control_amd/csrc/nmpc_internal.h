@@ -43,6 +43,21 @@ struct ClParams {
     int noise_len;
     double *acc;      // [B][4] cost, aed numerator, failures, steps
 };
+// closed-loop history (nmpc_closed_loop_set_history; x null: off): per (step, instance) the state the step
+// started from, the input the plant received and the solve status, rows [step - origin][B][...]; steps outside
+// [origin, origin + cap) are not stored. A block of its own at the end of the kernels' parameters (never inside
+// ClParams, which IpmParams embeds: the existing members keep their offsets).
+struct HistParams {
+    double *x, *u;   // [cap][B][nx], [cap][B][nu]
+    int *status;     // [cap][B]
+    int origin, cap;
+};
+// the history row of closed-loop step `step`, or -1 (before the origin or past the capacity: not stored)
+__host__ __device__ inline int hist_row(int step, int origin, int cap)
+{
+    const int row = step - origin;
+    return row >= 0 && row < cap ? row : -1;
+}
 // Kernel parameters of the batched IPM solve (nmpc_ipm.hip). All pointers are device
 // pointers. Model data (AB..ubnd) is shared by every instance of a handle.
 template <typename T>
@@ -106,6 +121,7 @@ struct IpmParams {
     signed char *cl_flags;
     const int *cl_eslot;
     int cl_nslot;
+    HistParams hist;              // fused closed loop / list mode: read by the recording instantiations only
 };
 
 // Lean fused closed loop (nmpc_cl_fast.hip): the exact finish's fast path, one wavefront per
@@ -181,6 +197,11 @@ struct ClFastParams {
     // whose unconstrained solutions z_0 sf_kernel wrote to xout / uout (z0_xu = 1: z_0 read from there)
     const int *work_list, *work_count;
     int z0_xu;
+    // closed-loop history (HistParams): written by the recording instantiations of cl_fast_kernel /
+    // cl_lock_kernel only, which cl_fast_launch picks when hist_x is set (the default ones never read these)
+    double *hist_x, *hist_u;
+    int *hist_status;
+    int hist_origin, hist_cap;
 };
 // fp32 handles' exact finish of a solve (nmpc_cl_fast.hip): z_0 = M [x0; yref] + vc for every element on the
 // f32 matrix cores, then per instance the lean loop's active-set machinery (fp64 W, solves and acceptance)
@@ -326,7 +347,21 @@ hipError_t cl_prepare_launch(const ClParams<T> &p, hipStream_t s);
 template <typename T>
 hipError_t cl_noise_launch(const ClParams<T> &p, int step0, int nsteps, double *out, hipStream_t s, int *zero2 = nullptr);
 template <typename T>
-hipError_t cl_advance_launch(const ClParams<T> &p, hipStream_t s);
+hipError_t cl_advance_launch(const ClParams<T> &p, const HistParams &hs, hipStream_t s);
+// history prefill of rows [0, cap): x / u NaN, status -1 (unwritten)
+hipError_t hist_fill_launch(double *hx, double *hu, int *hs, size_t nxe, size_t nue, size_t nse, hipStream_t s);
+// the batch's tracking-error envelope of history rows [row0, row0 + nrows): out[row][4] = sum_b e, max_b e,
+// instances with status != 0, instances recorded; e = sum_{i < aed_dims} |table[(offset_b + step) % period][i] - x_i|
+// (table: the handle's, fp64 or fp32 by `f64`)
+struct HistEnvParams {
+    int B, nx, aed_dims, period, table_cols, origin, row0, nrows, f64;
+    const void *table;
+    const int *offset;
+    const double *hist_x;
+    const int *hist_status;
+    double *out;   // [nrows][4]
+};
+hipError_t hist_envelope_launch(const HistEnvParams &p, hipStream_t s);
 
 // plant simulator (nmpc_plant.hip)
 hipError_t plant_step_launch(int batch, int num_stages, double T, double mass, double g,

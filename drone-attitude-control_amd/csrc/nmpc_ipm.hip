@@ -300,7 +300,7 @@ struct Geometry {
 #define NMPC_PTICK(slot) ((void)0)
 #endif
 
-template <typename T, int NX, int NU, int IPW, int WPB, int MW>
+template <typename T, int NX, int NU, int IPW, int WPB, int MW, bool REC = false>
 __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(MW, 8))) void ipm_kernel(IpmParams<T> p)
 {
     using Gm = Geometry<T, NX, NU, IPW, WPB>;
@@ -1169,8 +1169,8 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(MW, 8)
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             if (inst_ok)
-                cl_advance_group<T, NX, NU>(p.cl, inst, p.cl.step + cstep, status < 0 ? 0 : status, ll,
-                                            p.cl_noise[(size_t)inst * nsteps + cstep]);
+                cl_advance_group<T, NX, NU, REC>(p.cl, inst, p.cl.step + cstep, status < 0 ? 0 : status, ll,
+                                                 p.cl_noise[(size_t)inst * nsteps + cstep], p.hist);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -1184,7 +1184,9 @@ static hipError_t launch_ipm(const IpmParams<T> &p, hipStream_t s)
 {
     const int waves = (p.B + IPW - 1) / IPW;
     const int blocks = (waves + WPB - 1) / WPB;
-    NMPC_LAUNCH((ipm_kernel<T, NX, NU, IPW, WPB, MW>), dim3(blocks), dim3(64 * WPB), 0, s, p);
+    // closed-loop history armed (fused steps): the recording instantiation, the same launch shape
+    if (p.cl_steps > 0 && p.hist.x) NMPC_LAUNCH((ipm_kernel<T, NX, NU, IPW, WPB, MW, true>), dim3(blocks), dim3(64 * WPB), 0, s, p);
+    else NMPC_LAUNCH((ipm_kernel<T, NX, NU, IPW, WPB, MW>), dim3(blocks), dim3(64 * WPB), 0, s, p);
     return hipGetLastError();
 }
 

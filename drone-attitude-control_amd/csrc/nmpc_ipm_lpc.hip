@@ -258,7 +258,7 @@ struct Buf {
     }
 };
 
-template <typename T, int NX, int NU, int WPB, int MW, class SP>
+template <typename T, int NX, int NU, int WPB, int MW, class SP, bool REC = false>
 __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(MW, 8))) void ipm_lpc_kernel(IpmParams<T> p)
 {
     // rows of [A B] per SGPR chunk: ~16 loaded elements per chunk
@@ -2269,6 +2269,15 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(MW, 8)
                 // yref row 0), then x <- [A B] [x; u_0] + c + noise
                 const int nc = p.cl.ncl, na_ = p.cl.aed_dims;
                 const T xs = clx[r];
+                if (REC && inst_ok) {   // history (nmpc_cl_device.h): the x-lanes the state, the u-lanes u_0
+                    const int row = hist_row(cl_base + cstep, p.hist.origin, p.hist.cap);
+                    if (row >= 0) {
+                        const size_t o = (size_t)row * p.cl.B + inst;
+                        if (xl) p.hist.x[o * NX + r] = (double)xs;
+                        else p.hist.u[o * NU + u] = (double)clz[r];
+                        if (r == 0) p.hist.status[o] = status < 0 ? 0 : status;
+                    }
+                }
                 const double e_ = (double)xs - (double)cly[r];
                 double ce = (xl && r < nc) ? (double)p.cl.wcl[r] * e_ * e_ : 0.0;
                 double ae = (xl && r < na_) ? fabs(e_) : 0.0;
@@ -2300,9 +2309,10 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(MW, 8)
                     cls[3] += T(1);
                 }
             } else if (inst_ok) {
-                cl_advance_group<T, NX, NU>(p.cl, inst, cl_base + cstep, status < 0 ? 0 : status, r,
+                cl_advance_group<T, NX, NU, REC>(p.cl, inst, cl_base + cstep, status < 0 ? 0 : status, r,
                                             lmode ? p.cl_noise[(size_t)inst * p.cl_noise_ld + (cl_base + cstep - p.cl_noise_step0)]
-                                                  : p.cl_noise[(size_t)inst * nsteps + cstep]);
+                                                  : p.cl_noise[(size_t)inst * nsteps + cstep],
+                                                 p.hist);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();
@@ -2354,7 +2364,9 @@ hipError_t launch_ipm_lpc(const IpmParams<T> &p, hipStream_t s)
     const int waves = ((p.cl_list ? p.cl_count : p.B) + Gm::IPW - 1) / Gm::IPW;
     const int blocks = (waves + WPB - 1) / WPB;
     if (blocks < 1) return hipSuccess;
-    NMPC_LAUNCH((lpc::ipm_lpc_kernel<T, NX, NU, WPB, MW, SP>), dim3(blocks), dim3(64 * WPB), 0, s, p);
+    // closed-loop history armed (fused steps, list mode): the recording instantiation, the same launch shape
+    if (p.cl_steps > 0 && p.hist.x) NMPC_LAUNCH((lpc::ipm_lpc_kernel<T, NX, NU, WPB, MW, SP, true>), dim3(blocks), dim3(64 * WPB), 0, s, p);
+    else NMPC_LAUNCH((lpc::ipm_lpc_kernel<T, NX, NU, WPB, MW, SP>), dim3(blocks), dim3(64 * WPB), 0, s, p);
     return hipGetLastError();
 }
 

@@ -288,6 +288,46 @@ int nmpc_closed_loop_set_outputs(nmpc_solver *h, int on);
 /* current closed-loop states, batch*nx */
 int nmpc_closed_loop_get_state(nmpc_solver *h, double *out, size_t count);
 
+/* Closed-loop history (opt-in; default off): the trajectory of every instance, recorded on the device by
+ * whichever path runs the steps (lean loop, fused, per step, the list-mode fallback), with no extra launch
+ * and no host wait. While armed, each closed-loop step s of each instance b stores
+ *   x      nx doubles: the controller state the step started from (the pinned x0; Xsim[s] of controller.py's
+ *          follow_trajectory, plus the acceleration part for the jerk model),
+ *   u      nu doubles: the input the plant step received (the clamped u_0, or the failure input),
+ *   status int32: the step's solve status
+ * into device planes [step][batch][nx | nu | 1], always double / int32 (fp32 handles widen their state at the
+ * store). Rows are indexed by the absolute closed-loop step minus the origin; steps at or beyond the capacity
+ * are not stored (no ring). Each (step, instance) row has exactly one writer. With history off, results,
+ * launches and kernels are what they were; with it on the lean loop launches the recording instantiation of
+ * its kernels. Device bytes: capacity * batch * ((nx + nu) * 8 + 4).
+ *
+ * capacity_steps > 0: allocate and arm; the origin is the loop's current step. Waits for the stream.
+ * Prefills x / u with NaN and status with -1. Calling again re-arms with a new origin.
+ * capacity_steps == 0: free and turn off.
+ * NMPC_ESTATE before nmpc_closed_loop_init (which also turns history off).
+ * NMPC_ENOMEM when the allocation fails: the handle stays usable, history off. */
+int nmpc_closed_loop_set_history(nmpc_solver *h, int capacity_steps);
+/* out[0] origin step, out[1] capacity, out[2] steps recorded so far
+ * (min(capacity, steps run since origin)), out[3] device bytes held; n <= 4 values are written
+ * (history off: all 0) */
+int nmpc_closed_loop_history_info(nmpc_solver *h, long long *out, int n);
+/* field "x" | "u"; steps relative to the origin; out[nsteps][ninst][nx|nu]; count checked.
+ * Waits for the stream. A range outside [0, recorded) x [0, batch) is NMPC_EINVAL; NMPC_ESTATE with
+ * history off. A row no step wrote reads NaN. */
+int nmpc_closed_loop_get_history(nmpc_solver *h, const char *field, int inst0, int ninst,
+                                 int step0, int nsteps, double *out, size_t count);
+/* field "status": out[nsteps][ninst]; -1: no step wrote the row */
+int nmpc_closed_loop_get_history_int(nmpc_solver *h, const char *field, int inst0, int ninst,
+                                     int step0, int nsteps, int32_t *out, size_t count);
+/* the batch's tracking-error envelope over recorded steps [step0, step0 + nsteps), one device reduction
+ * (nothing but nsteps*4 doubles is downloaded): out[nsteps][4] =
+ *   [ sum_b e(b,s), max_b e(b,s), instances with status != 0, instances recorded ],
+ * e(b,s) = sum_{i < aed_dims} |table[(offset_b + s) % period][i] - x(b,s)[i]| (s absolute), the loop's AED
+ * numerator term. Instances whose row was not written are skipped and not counted. The reduction order is
+ * fixed (no floating-point atomics): two calls return the same bits. Waits for the stream. */
+int nmpc_closed_loop_history_envelope(nmpc_solver *h, int step0, int nsteps,
+                                      double *out, size_t count);
+
 /* plant simulator (AcadosSimSolver for src/plant.py:27-43): one step of the nonlinear 2-D
  * Crazyflie plant x=[px,pz,vx,vz], u=[theta, F_d] on the device for `batch` states.
  *   method NMPC_ERK, num_stages 4 over T (force_model/ocp.py:98-104), or
