@@ -19,6 +19,9 @@ NMPC_IRK, NMPC_ERK = 0, 1
 NMPC_COST_SCALING_TIME_STEPS, NMPC_COST_SCALING_NONE = 0, 1
 NMPC_ABI_VERSION = 2
 
+NMPC_EINVAL, NMPC_EDEVICE, NMPC_ENOMEM, NMPC_EUNSUPPORTED, NMPC_ESTATE = -1, -2, -3, -4, -5
+NMPC_SENS_OK, NMPC_SENS_DEGENERATE, NMPC_SENS_NO_SOLUTION, NMPC_SENS_SET_TOO_LARGE = 0, 1, 2, 3
+
 STATUS_TEXT = {0: "success", 1: "failure", 2: "maximum number of iterations reached",
                3: "minimum step size in QP solver reached", 4: "qp solver failed"}
 
@@ -103,6 +106,11 @@ SIGNATURES = {
                                                         ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
                                                         ctypes.c_size_t]),
     "nmpc_closed_loop_history_envelope": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_size_t]),
+    "nmpc_sens_forward_async": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "nmpc_sens_forward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _dp, ctypes.c_size_t, _dp, ctypes.c_size_t]),
+    "nmpc_sens_adjoint_async": (ctypes.c_int, [ctypes.c_void_p]),
+    "nmpc_sens_adjoint": (ctypes.c_int, [ctypes.c_void_p, _dp, ctypes.c_size_t, _dp, ctypes.c_size_t,
+                                         _dp, ctypes.c_size_t, _dp, ctypes.c_size_t]),
     "nmpc_sim_plant": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                       ctypes.c_double, _dp, _dp, _dp]),
 }

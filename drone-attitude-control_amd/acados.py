@@ -416,6 +416,67 @@ class AcadosOcpSolver:
     def synchronize(self):
         return self._check(self.lib.nmpc_synchronize(self._h), "synchronize")
 
+    # -------------------------------------------------------------- solution sensitivities
+    def sens_forward_async(self, stage):
+        """Enqueue d(x_stage, u_stage)/d x0bar of every instance behind the solve on the handle's stream
+        (results in device_ptr("sens_x") / ("sens_u") / ("sens_status")); no host wait."""
+        return self._check(self.lib.nmpc_sens_forward_async(self._h, int(stage)), "sens_forward_async")
+
+    def sens_adjoint_async(self):
+        """Enqueue the adjoint of the cotangents in device_ptr("seed_x") / ("seed_u") (results in
+        device_ptr("grad_x0") / ("grad_yref")); no host wait."""
+        return self._check(self.lib.nmpc_sens_adjoint_async(self._h), "sens_adjoint_async")
+
+    def sens_batch(self, stage):
+        """(sens_x [B, nx, nx], sens_u [B, nu, nx] or None at stage N, status [B]) of the solution in the
+        device outputs: d x_stage / d x0bar and d u_stage / d x0bar on the region where the active set holds
+        (status: NMPC_SENS_* per instance; 2 / 3: NaN rows)."""
+        stage = int(stage)
+        sx = np.zeros((self.batch, self.nx, self.nx))
+        su = np.zeros((self.batch, self.nu, self.nx)) if stage != self.N else None
+        self._check(self.lib.nmpc_sens_forward(self._h, stage, _lib.dptr(sx), sx.size, _lib.dptr(su),
+                                               su.size if su is not None else 0), f"sens_batch({stage})")
+        return sx, su, self.get_batch_int("sens_status")
+
+    def adjoint_batch(self, grad_x=None, grad_u=None):
+        """Vector-Jacobian product of the solve: cotangents grad_x [B, N+1, nx] / grad_u [B, N, nu] on the
+        solution (None: zero) pulled back to (grad_x0 [B, nx], grad_yref [B, N*ny + ny_e], status [B])."""
+        gx = None if grad_x is None else _lib.f64(grad_x, (self.batch, self.N + 1, self.nx))
+        gu = None if grad_u is None else _lib.f64(grad_u, (self.batch, self.N, self.nu))
+        g0 = np.zeros((self.batch, self.nx))
+        gy = np.zeros((self.batch, self.N * self.ny + self.ny_e))
+        self._check(self.lib.nmpc_sens_adjoint(self._h, _lib.dptr(gx), gx.size if gx is not None else 0,
+                                               _lib.dptr(gu), gu.size if gu is not None else 0,
+                                               _lib.dptr(g0), g0.size, _lib.dptr(gy), gy.size), "adjoint_batch")
+        return g0, gy, self.get_batch_int("sens_status")
+
+    def eval_solution_sensitivity(self, stages, with_respect_to="initial_state", return_sens_x=True,
+                                  return_sens_u=True, instance=0):
+        """acados's AcadosOcpSolver.eval_solution_sensitivity(stages, "initial_state"): {"sens_x": dx_stage/dx0bar,
+        "sens_u": du_stage/dx0bar} of one instance; an int stage gives arrays, a list of stages lists. Any other
+        `with_respect_to` raises NotImplementedError. (`instance` is the batched extension.)"""
+        if with_respect_to != "initial_state":
+            raise NotImplementedError(f"eval_solution_sensitivity: with_respect_to='{with_respect_to}' "
+                                      "(only 'initial_state' is available)")
+        single = isinstance(stages, (int, np.integer))
+        out_x, out_u = [], []
+        for k in ([stages] if single else list(stages)):
+            k = int(k)
+            # acados returns no sens_u at the terminal stage either (nu = 0 there)
+            sx = np.zeros((self.batch, self.nx, self.nx)) if return_sens_x else None
+            su = np.zeros((self.batch, self.nu, self.nx)) if return_sens_u and k != self.N else None
+            self._check(self.lib.nmpc_sens_forward(self._h, k, _lib.dptr(sx), sx.size if sx is not None else 0,
+                                                   _lib.dptr(su), su.size if su is not None else 0),
+                        f"eval_solution_sensitivity({k})")
+            out_x.append(sx[instance] if sx is not None else None)
+            out_u.append(su[instance] if su is not None else (np.zeros((0, self.nx)) if return_sens_u else None))
+        res = {}
+        if return_sens_x:
+            res["sens_x"] = out_x[0] if single else out_x
+        if return_sens_u:
+            res["sens_u"] = out_u[0] if single else out_u
+        return res
+
     def set_stream(self, stream_ptr):
         return self._check(self.lib.nmpc_set_stream(self._h, ctypes.c_void_p(stream_ptr)), "set_stream")
 

@@ -279,6 +279,17 @@ struct nmpc_solver {
     double *d_hist_x = nullptr, *d_hist_u = nullptr;
     int *d_hist_s = nullptr;
     int hist_origin = 0, hist_cap = 0;
+    // solution sensitivities (nmpc_sens_*, nmpc_sens.hip; fp64 handles): allocated at the first call
+    bool dev_solution = false;             // the device x / u / status hold a solution (a solve, or the lean loop's
+                                           // last step with nmpc_closed_loop_set_outputs on)
+    double *d_sens = nullptr;              // T_x [ne][nx], sens_x, sens_u, seed_x, seed_u, grad_x0, grad_yref
+    size_t senso[7] = {0, 0, 0, 0, 0, 0, 0};
+    double *d_sens_vy = nullptr;           // V_y [ne][ystride] (the first adjoint call)
+    int *d_sens_status = nullptr;          // [B]
+    int sens_res[2] = {0, 0};              // resident workgroups of the forward / adjoint kernel
+    std::vector<int32_t> h_sens_status;    // as downloaded by the last nmpc_sens_forward / nmpc_sens_adjoint
+    bool sens_status_valid = false;
+    std::vector<double> h_seed[2];         // host staging of nmpc_sens_adjoint's cotangents
     double *d_fnoise = nullptr;   // fused closed loop: noise draws of a launch's steps [B][64]
     int *d_iter_log = nullptr;    // fused closed loop, env NMPC_ITER_LOG: per-step finish steps | IPM iterations << 8 | status << 16 [64][B]
     int iter_log_steps = 0;       // steps in the log (the last fused launch; the lean loop: the last run)
@@ -543,7 +554,8 @@ void free_all(nmpc_solver *h)
                     (void *)h->d_istep, (void *)h->d_park, (void *)h->d_flags, h->d_clf_scratch, (void *)h->d_clw,
                     (void *)h->d_fin_f, (void *)h->d_fin_i, (void *)h->d_z0, (void *)h->d_sf, (void *)h->d_f64,
                     (void *)h->d_f64i, (void *)h->d_sfl, h->d_sf_scratch, (void *)h->d_sfcyc, (void *)h->d_clf_check, (void *)h->d_imap,
-                    (void *)h->d_gorder, (void *)h->d_hist_x, (void *)h->d_hist_u, (void *)h->d_hist_s})
+                    (void *)h->d_gorder, (void *)h->d_hist_x, (void *)h->d_hist_u, (void *)h->d_hist_s,
+                    (void *)h->d_sens, (void *)h->d_sens_vy, (void *)h->d_sens_status})
         if (p) hipFree(p);
     if (h->h_sfpark) hipHostFree(h->h_sfpark);
     if (h->ev_fb) hipEventDestroy(h->ev_fb);
@@ -775,6 +787,11 @@ int launch(nmpc_solver *h, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, int
 }
 
 int field_is(const char *f, const char *name) { return f && std::strcmp(f, name) == 0; }
+
+// solution sensitivities (defined with nmpc_sens_* below): the device buffers of the handle, allocated at the first
+// use (adjoint: V_y too); the index of a sensitivity field of nmpc_device_ptr (0 "sens_status", else into senso), or -1
+int sens_ensure(nmpc_solver *h, const char *fn, bool adjoint);
+int sens_field(const char *field);
 
 }  // namespace
 
@@ -1325,6 +1342,12 @@ int nmpc_get_batch(nmpc_solver *h, const char *field, double *out, size_t count)
 int nmpc_get_batch_int(nmpc_solver *h, const char *field, int32_t *out, size_t count)
 {
     if (!h || !field || !out) return NMPC_EINVAL;
+    if (field_is(field, "sens_status")) {   // of the last nmpc_sens_forward / nmpc_sens_adjoint
+        if (!h->sens_status_valid) return h->fail(NMPC_ESTATE, "nmpc_get_batch_int: no sensitivity call has completed");
+        if (count != h->h_sens_status.size()) return h->fail(NMPC_EINVAL, "nmpc_get_batch_int: size mismatch");
+        std::memcpy(out, h->h_sens_status.data(), count * sizeof(int32_t));
+        return 0;
+    }
     if (!h->out_valid) return h->fail(NMPC_ESTATE, "nmpc_get_batch_int: no solution available");
     const std::vector<int32_t> *src =
         field_is(field, "status") ? &h->h_status : field_is(field, "qp_iter") ? &h->h_iters : nullptr;
@@ -1343,6 +1366,11 @@ int nmpc_device_ptr(nmpc_solver *h, const char *field, void **out)
     else if (field_is(field, "u")) *out = h->d_u;
     else if (field_is(field, "status")) *out = h->d_status;
     else if (field_is(field, "qp_iter")) *out = h->d_iters;
+    else if (const int si = sens_field(field); si >= 0) {   // allocated at the first use
+        const int r = sens_ensure(h, "nmpc_device_ptr", false);
+        if (r < 0) return r;
+        *out = si == 0 ? (void *)h->d_sens_status : (void *)(h->d_sens + h->senso[si]);
+    }
     else return h->fail(NMPC_EINVAL, std::string("nmpc_device_ptr: unknown field '") + field + "'");
     return 0;
 }
@@ -1352,7 +1380,9 @@ int nmpc_solve_async(nmpc_solver *h)
     if (!h) return NMPC_EINVAL;
     hipSetDevice(h->device);
     h->out_valid = false;
-    return h->precision == NMPC_FP64 ? launch<double>(h) : launch<float>(h);
+    const int r = h->precision == NMPC_FP64 ? launch<double>(h) : launch<float>(h);
+    if (r >= 0) h->dev_solution = true;   // (in stream order: what nmpc_sens_* enqueued behind it differentiates)
+    return r;
 }
 
 // The host's wait for the handle's stream. hipStreamSynchronize parks the thread once its short active wait has
@@ -1434,6 +1464,7 @@ int nmpc_solve(nmpc_solver *h)
     }
     int r = h->precision == NMPC_FP64 ? launch<double>(h) : launch<float>(h);
     if (r < 0) return r;
+    h->dev_solution = true;
     if ((r = download_outputs(h)) < 0) return r;   // waits for the stream
     if ((r = sf_resolve(h)) < 0) return r;         // fast solve: its listed / parked counts
     h->out_from_loop = false;
@@ -1686,6 +1717,33 @@ int ensure_w64(nmpc_solver *h)
     return e == hipSuccess ? 0 : hip_fail(h, e, "fp64 W table upload");
 }
 
+// The unconstrained solution's explicit maps, by unconstrained Riccati solves on the host (lqr_host): T_x, its
+// response to x0 ([ne][nx] into tx, row pitch ldx), and V_y, its response to each reference component of the
+// stage-stacked yref ([ne][ystride] into vy, row pitch ldy). Shared by the fp32 finish (M = [T_x | V_y]) and the
+// solution sensitivities.
+void explicit_maps(const nmpc_solver *h, bool want_tx, bool want_vy, double *tx, size_t ldx, double *vy, size_t ldy)
+{
+    const int nx = h->nx, nu = h->nu, nz = nx + nu, N = h->N, ne = (N + 1) * nz;
+    const int ny = h->ny, nye = h->ny_e, ys = (int)h->ystride();
+    std::vector<double> g(ne, 0.0), z(ne), e0(nx, 0.0);
+    for (int j = 0; want_tx && j < nx; j++) {   // T_x
+        std::fill(e0.begin(), e0.end(), 0.0);
+        e0[j] = 1.0;
+        lqr_solve(nx, nu, N, h->A, h->B, h->c, h->lqr_host, g.data(), e0.data(), false, z.data());
+        for (int e = 0; e < ne; e++) tx[(size_t)e * ldx + j] = z[e];
+    }
+    std::fill(e0.begin(), e0.end(), 0.0);
+    for (int q = 0; want_vy && q < ys; q++) {   // V_y: reference component q of the stage-stacked yref
+        const int k = q < N * ny ? q / ny : N, c_ = q < N * ny ? q % ny : q - N * ny;
+        const int n = k < N ? nz : nx, m = k < N ? ny : nye;
+        const double *Gm = k < N ? h->G.data() : h->Ge.data();
+        std::fill(g.begin(), g.end(), 0.0);
+        for (int i = 0; i < n; i++) g[(size_t)k * nz + i] = Gm[i * m + c_];
+        lqr_solve(nx, nu, N, h->A, h->B, h->c, h->lqr_host, g.data(), e0.data(), false, z.data());
+        for (int e = 0; e < ne; e++) vy[(size_t)e * ldy + q] = z[e];
+    }
+}
+
 // The exact finish of fp32 solves (nmpc_cl_fast.hip fin32_*): for the lean loop's shapes with diagonal
 // costs (env NMPC_FIN32=0: off). M = [T_x | V_y] and vc, the unconstrained solution's response to x0, to
 // each reference component (stage-stacked as h_yref) and to c, by unconstrained Riccati solves on the host.
@@ -1697,26 +1755,11 @@ int fin32_setup(nmpc_solver *h)
     std::vector<int> el, fr;
     std::vector<double> lb, ub, uinit;
     if (!slot_layout(h, el, fr, lb, ub, uinit) || nmpc::fin32_resident(nx, nu, (int)el.size(), h->device) <= 0) return 0;
-    const int ny = h->ny, nye = h->ny_e, ys = (int)h->ystride(), K = nx + ys;
+    const int ys = (int)h->ystride(), K = nx + ys;
     const int m16 = (ne + 15) / 16 * 16, kp = (K + 3) / 4 * 4;
     std::vector<double> M((size_t)m16 * kp, 0.0), vc(m16, 0.0), g(ne, 0.0), z(ne), e0(nx, 0.0);
-    for (int j = 0; j < nx; j++) {   // T_x
-        std::fill(e0.begin(), e0.end(), 0.0);
-        e0[j] = 1.0;
-        lqr_solve(nx, nu, N, h->A, h->B, h->c, h->lqr_host, g.data(), e0.data(), false, z.data());
-        for (int e = 0; e < ne; e++) M[(size_t)e * kp + j] = z[e];
-    }
-    std::fill(e0.begin(), e0.end(), 0.0);
-    for (int q = 0; q < ys; q++) {   // V_y: reference component q of the stage-stacked yref
-        const int k = q < N * ny ? q / ny : N, c_ = q < N * ny ? q % ny : q - N * ny;
-        const int n = k < N ? nz : nx, m = k < N ? ny : nye;
-        const double *Gm = k < N ? h->G.data() : h->Ge.data();
-        std::fill(g.begin(), g.end(), 0.0);
-        for (int i = 0; i < n; i++) g[(size_t)k * nz + i] = Gm[i * m + c_];
-        lqr_solve(nx, nu, N, h->A, h->B, h->c, h->lqr_host, g.data(), e0.data(), false, z.data());
-        for (int e = 0; e < ne; e++) M[(size_t)e * kp + nx + q] = z[e];
-    }
-    std::fill(g.begin(), g.end(), 0.0);   // vc: the response to c
+    explicit_maps(h, true, true, M.data(), kp, M.data() + nx, kp);   // T_x | V_y
+    // vc: the response to c
     lqr_solve(nx, nu, N, h->A, h->B, h->c, h->lqr_host, g.data(), e0.data(), true, z.data());
     for (int e = 0; e < ne; e++) vc[e] = z[e];
     const std::vector<double> *parts[5] = {&lb, &ub, &uinit, &M, &vc};
@@ -2733,6 +2776,8 @@ int nmpc_closed_loop_run(nmpc_solver *h, int steps, int sync)
     const char *fused_env = std::getenv("NMPC_CL_FUSED");
     const bool lean = h->clf && !(fused_env && fused_env[0] == '0');
     h->clf_parked = h->clf_rounds = 0;
+    // the device x / u hold a solution afterwards only where the lean loop writes its last step's trajectories
+    if (steps > 0) h->dev_solution = lean && h->cl_traj_out;
     if (lean) {
         launches = steps <= 0 ? 0 : (h->precision == NMPC_FP64 ? clf_run<double>(h, steps, !sync) : clf_run<float>(h, steps, !sync));
         if (launches < 0) return launches;
@@ -2976,6 +3021,220 @@ int nmpc_closed_loop_history_envelope(nmpc_solver *h, int step0, int nsteps, dou
     if (e == hipSuccess) e = ef;
     if (e != hipSuccess) return hip_fail(h, e, "nmpc_closed_loop_history_envelope");
     return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ solution sensitivities (nmpc_sens.hip)
+namespace {
+
+int sens_field(const char *f)
+{
+    static const char *names[7] = {"sens_status", "sens_x", "sens_u", "seed_x", "seed_u", "grad_x0", "grad_yref"};
+    for (int i = 0; i < 7; i++)
+        if (field_is(f, names[i])) return i;
+    return -1;
+}
+
+// element counts of the handle's sensitivity buffers in senso order: T_x, sens_x, sens_u, seed_x, seed_u, grad_x0, grad_yref
+void sens_counts(const nmpc_solver *h, size_t n[7])
+{
+    const size_t B = h->batch, nx = h->nx, nu = h->nu, N = h->N;
+    n[0] = (N + 1) * (nx + nu) * nx;
+    n[1] = B * nx * nx;
+    n[2] = B * nu * nx;
+    n[3] = B * (N + 1) * nx;
+    n[4] = B * N * nu;
+    n[5] = B * nx;
+    n[6] = B * h->ystride();
+}
+
+// what the handle must be for the sensitivity calls (NMPC_EUNSUPPORTED with the reason), then the buffers
+int sens_ensure(nmpc_solver *h, const char *fn, bool adjoint)
+{
+    const std::string f(fn);
+    if (h->precision != NMPC_FP64) return h->fail(NMPC_EUNSUPPORTED, f + ": solution sensitivities need an fp64 handle");
+    if (!nmpc::sens_shape(h->nx, h->nu))
+        return h->fail(NMPC_EUNSUPPORTED, f + ": no sensitivity kernel for nx=" + std::to_string(h->nx) + " nu=" + std::to_string(h->nu) +
+                                              " (compiled: 4/2, 6/2, 13/4)");
+    if (h->lqr_host.empty() || h->cond)
+        return h->fail(NMPC_EUNSUPPORTED, f + ": the handle has no unconstrained tables (condensed family, or the exact finish off)");
+    const int ne = (h->N + 1) * (h->nx + h->nu);
+    if (ne > nmpc::SENS_GMAX)
+        return h->fail(NMPC_EUNSUPPORTED, f + ": (N + 1)(nx + nu) = " + std::to_string(ne) + " exceeds " + std::to_string(nmpc::SENS_GMAX));
+    hipSetDevice(h->device);
+    hipError_t e = hipSuccess;
+    if (!h->d_sens) {
+        size_t n[7], tot = 0;
+        sens_counts(h, n);
+        for (int i = 0; i < 7; i++) {
+            h->senso[i] = tot;
+            tot += (n[i] + 31) & ~(size_t)31;
+        }
+        h->sens_res[0] = nmpc::sens_resident(h->nx, h->nu, 0, h->device);
+        h->sens_res[1] = nmpc::sens_resident(h->nx, h->nu, 1, h->device);
+        if (h->sens_res[0] <= 0 || h->sens_res[1] <= 0) return h->fail(NMPC_EDEVICE, f + ": occupancy query of the sensitivity kernels");
+        std::vector<double> tx(n[0]);
+        explicit_maps(h, true, false, tx.data(), h->nx, nullptr, 0);
+        double *d = nullptr;
+        int *ds = nullptr;
+        if (hipMalloc((void **)&d, tot * sizeof(double)) != hipSuccess) return h->fail(NMPC_ENOMEM, f + ": sensitivity buffers");
+        if (hipMalloc((void **)&ds, (size_t)h->batch * sizeof(int)) != hipSuccess) {
+            hipFree(d);
+            return h->fail(NMPC_ENOMEM, f + ": sensitivity buffers");
+        }
+        // (plain copies: complete before any later launch on the handle's stream is enqueued)
+        e = hipMemset(d, 0, tot * sizeof(double));   // zero cotangents until the caller writes them
+        if (e == hipSuccess) e = hipMemset(ds, 0, (size_t)h->batch * sizeof(int));
+        if (e == hipSuccess) e = hipMemcpy(d, tx.data(), tx.size() * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            hipFree(d);
+            hipFree(ds);
+            return hip_fail(h, e, (f + ": sensitivity tables").c_str());
+        }
+        h->d_sens = d;
+        h->d_sens_status = ds;
+        h->h_sens_status.assign(h->batch, 0);
+    }
+    if (adjoint && !h->d_sens_vy) {
+        const size_t ys = h->ystride();
+        std::vector<double> vy((size_t)ne * ys);
+        explicit_maps(h, false, true, nullptr, 0, vy.data(), ys);
+        double *d = nullptr;
+        if (hipMalloc((void **)&d, vy.size() * sizeof(double)) != hipSuccess) return h->fail(NMPC_ENOMEM, f + ": V_y table");
+        e = hipMemcpy(d, vy.data(), vy.size() * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            hipFree(d);
+            return hip_fail(h, e, (f + ": V_y table").c_str());
+        }
+        h->d_sens_vy = d;
+    }
+    return 0;
+}
+
+// one sensitivity launch on the handle's stream, behind whatever produced the device solution
+int sens_enqueue(nmpc_solver *h, const char *fn, bool adjoint, int stage)
+{
+    int r = sens_ensure(h, fn, adjoint);
+    if (r < 0) return r;
+    if (stage < 0 || stage > h->N)
+        return h->fail(NMPC_EINVAL, std::string(fn) + ": stage " + std::to_string(stage) + " outside [0, N]");
+    if (!h->dev_solution)
+        return h->fail(NMPC_ESTATE, std::string(fn) + ": the device outputs hold no solution (solve first, or run the lean "
+                                                      "closed loop with nmpc_closed_loop_set_outputs on)");
+    const char *m = (const char *)h->d_model;
+    nmpc::SensParams p{};
+    p.B = h->batch;
+    p.N = h->N;
+    p.ne = (h->N + 1) * (h->nx + h->nu);
+    p.ystride = (int)h->ystride();
+    p.stage = stage;
+    p.W = (const double *)(m + h->off_lqrw);
+    p.tx = h->d_sens + h->senso[0];
+    p.vy = h->d_sens_vy;
+    p.lbnd = (const double *)(m + h->off_lb);
+    p.ubnd = (const double *)(m + h->off_ub);
+    p.x = (const double *)h->d_x;
+    p.u = (const double *)h->d_u;
+    p.status = h->d_status;
+    p.sens_x = h->d_sens + h->senso[1];
+    p.sens_u = h->d_sens + h->senso[2];
+    p.seed_x = h->d_sens + h->senso[3];
+    p.seed_u = h->d_sens + h->senso[4];
+    p.grad_x0 = h->d_sens + h->senso[5];
+    p.grad_yref = h->d_sens + h->senso[6];
+    p.sens_status = h->d_sens_status;
+    const hipError_t e = nmpc::sens_launch(h->nx, h->nu, adjoint ? 1 : 0, p, h->sens_res[adjoint ? 1 : 0], h->stream);
+    if (e != hipSuccess) return hip_fail(h, e, fn);
+    h->sens_status_valid = false;
+    return 0;
+}
+
+// the per-instance status to the host copy, then the wait; returns the largest status
+int sens_finish(nmpc_solver *h, const char *fn)
+{
+    hipError_t e = hipMemcpyAsync(h->h_sens_status.data(), h->d_sens_status, (size_t)h->batch * sizeof(int), hipMemcpyDeviceToHost,
+                                  h->stream);
+    if (e == hipSuccess) e = stream_wait(h->stream);
+    if (e != hipSuccess) return hip_fail(h, e, fn);
+    h->sens_status_valid = true;
+    int st = 0;
+    for (int b = 0; b < h->batch; b++) st = std::max(st, (int)h->h_sens_status[b]);
+    return st;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nmpc_sens_forward_async(nmpc_solver *h, int stage)
+{
+    if (!h) return NMPC_EINVAL;
+    return sens_enqueue(h, "nmpc_sens_forward_async", false, stage);
+}
+
+int nmpc_sens_forward(nmpc_solver *h, int stage, double *sens_x, size_t count_x, double *sens_u, size_t count_u)
+{
+    if (!h) return NMPC_EINVAL;
+    const char *fn = "nmpc_sens_forward";
+    int r = sens_ensure(h, fn, false);
+    if (r < 0) return r;
+    size_t n[7];
+    sens_counts(h, n);
+    if (stage < 0 || stage > h->N) return h->fail(NMPC_EINVAL, "nmpc_sens_forward: stage outside [0, N]");
+    if (stage == h->N && (sens_u || count_u)) return h->fail(NMPC_EINVAL, "nmpc_sens_forward: stage N has no u (sens_u must be NULL)");
+    if ((sens_x ? count_x != n[1] : count_x != 0) || (sens_u ? count_u != n[2] : count_u != 0))
+        return h->fail(NMPC_EINVAL, "nmpc_sens_forward: sens_x needs batch*nx*nx values, sens_u batch*nu*nx (a NULL output: count 0)");
+    if ((r = sens_enqueue(h, fn, false, stage)) < 0) return r;
+    hipError_t e = hipSuccess;
+    if (sens_x) e = hipMemcpyAsync(sens_x, h->d_sens + h->senso[1], n[1] * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && sens_u)
+        e = hipMemcpyAsync(sens_u, h->d_sens + h->senso[2], n[2] * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e != hipSuccess) return hip_fail(h, e, fn);
+    return sens_finish(h, fn);
+}
+
+int nmpc_sens_adjoint_async(nmpc_solver *h)
+{
+    if (!h) return NMPC_EINVAL;
+    return sens_enqueue(h, "nmpc_sens_adjoint_async", true, 0);
+}
+
+int nmpc_sens_adjoint(nmpc_solver *h, const double *gx, size_t cgx, const double *gu, size_t cgu, double *grad_x0, size_t c0,
+                      double *grad_yref, size_t cy)
+{
+    if (!h) return NMPC_EINVAL;
+    const char *fn = "nmpc_sens_adjoint";
+    int r = sens_ensure(h, fn, true);
+    if (r < 0) return r;
+    size_t n[7];
+    sens_counts(h, n);
+    if ((gx ? cgx != n[3] : cgx != 0) || (gu ? cgu != n[4] : cgu != 0))
+        return h->fail(NMPC_EINVAL, "nmpc_sens_adjoint: gx needs batch*(N+1)*nx values, gu batch*N*nu (a NULL cotangent: count 0)");
+    if ((grad_x0 ? c0 != n[5] : c0 != 0) || (grad_yref ? cy != n[6] : cy != 0))
+        return h->fail(NMPC_EINVAL, "nmpc_sens_adjoint: grad_x0 needs batch*nx values, grad_yref batch*(N*ny+ny_e) (a NULL output: count 0)");
+    if (!h->dev_solution) return h->fail(NMPC_ESTATE, "nmpc_sens_adjoint: the device outputs hold no solution");
+    // the cotangents in stream order (a NULL one is zero); the staging copy outlives the call
+    hipError_t e = hipSuccess;
+    const double *src[2] = {gx, gu};
+    for (int i = 0; i < 2 && e == hipSuccess; i++) {
+        double *dst = h->d_sens + h->senso[3 + i];
+        if (src[i]) {
+            h->h_seed[i].assign(src[i], src[i] + n[3 + i]);
+            e = hipMemcpyAsync(dst, h->h_seed[i].data(), n[3 + i] * sizeof(double), hipMemcpyHostToDevice, h->stream);
+        } else {
+            e = hipMemsetAsync(dst, 0, n[3 + i] * sizeof(double), h->stream);
+        }
+    }
+    if (e != hipSuccess) return hip_fail(h, e, fn);
+    if ((r = sens_enqueue(h, fn, true, 0)) < 0) return r;
+    if (grad_x0) e = hipMemcpyAsync(grad_x0, h->d_sens + h->senso[5], n[5] * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && grad_yref)
+        e = hipMemcpyAsync(grad_yref, h->d_sens + h->senso[6], n[6] * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e != hipSuccess) return hip_fail(h, e, fn);
+    return sens_finish(h, fn);
 }
 
 }  // extern "C"

@@ -269,6 +269,31 @@ hipError_t cl_fast_launch(int nx, int nu, int sid, int kind, const ClFastParams<
 // with rare-path steps in the previous launch, then the rest, each group in instance order (one workgroup)
 hipError_t clf_order_launch(const unsigned char *hard, int B, int *gorder, hipStream_t s);
 
+// Solution sensitivities (nmpc_sens.hip; fp64, the lean loop's shapes, any horizon with ne <= SENS_GMAX): one
+// wavefront per instance reads the active set S off the stored solution (x / u, the lean loop's on-bound rule),
+// factors W_SS in LDS and writes, forward: the rows of stage `stage` of dz/dx0 = T_x - W[:, S] W_SS^-1 T_x[S, :];
+// adjoint: [T_x | V_y]' (g - E_S' W_SS^-1 W[S, :] g) for the cotangent g = (seed_x, seed_u).
+constexpr int SENS_GMAX = 576;   // largest ne = (N + 1)(nx + nu) (the adjoint's cotangents in LDS: quad13 N <= 32)
+// per-instance status (include/nmpc.h NMPC_SENS_*)
+constexpr int NMPC_SENS_OK_ = 0, NMPC_SENS_DEGENERATE_ = 1, NMPC_SENS_NO_SOLUTION_ = 2, NMPC_SENS_SET_TOO_LARGE_ = 3;
+struct SensParams {
+    int B, N, ne, ystride, stage;
+    const double *W;              // [ne][ne] projected inverse Hessian (lqr_wmat; symmetric)
+    const double *tx;             // [ne][nx] T_x
+    const double *vy;             // [ne][ystride] V_y (adjoint only)
+    const double *lbnd, *ubnd;    // [3][nz]
+    const double *x, *u;          // the solution differentiated: [B][N+1][nx], [B][N][nu]
+    const int *status;            // [B] its solve status (!= 0: no solution)
+    const double *seed_x, *seed_u;   // adjoint: the cotangents in the layouts of x / u
+    double *sens_x, *sens_u;      // forward: [B][nx][nx], [B][nu][nx]
+    double *grad_x0, *grad_yref;  // adjoint: [B][nx], [B][ystride]
+    int *sens_status;             // [B]
+};
+bool sens_shape(int nx, int nu);
+// resident workgroups of the forward (adjoint = 0) / adjoint kernel on `device`; 0: none compiled
+int sens_resident(int nx, int nu, int adjoint, int device);
+hipError_t sens_launch(int nx, int nu, int adjoint, const SensParams &p, int resident, hipStream_t s);
+
 size_t scratch_elems_per_instance(int N, int nx, int nu);
 
 // returns an index into the kernel table (or -1), the chosen instances-per-wave, the

@@ -158,6 +158,8 @@ int nmpc_get(nmpc_solver *h, int instance, int stage, const char *field, double 
  *   "x"    batch*(N+1)*nx           (get)
  *   "u"    batch*N*nu               (get)
  *   "status", "qp_iter"  batch int32 (get; use nmpc_get_batch_int)
+ *   "sens_status"        batch int32 (nmpc_get_batch_int; the NMPC_SENS_* status of every instance as the last
+ *                        nmpc_sens_forward / nmpc_sens_adjoint downloaded it; NMPC_ESTATE before one completed)
  * `count` = number of doubles supplied / requested, checked against the layout. */
 int nmpc_set_batch(nmpc_solver *h, const char *field, const double *values, size_t count);
 int nmpc_get_batch(nmpc_solver *h, const char *field, double *out, size_t count);
@@ -165,7 +167,11 @@ int nmpc_get_batch_int(nmpc_solver *h, const char *field, int32_t *out, size_t c
 
 /* device-resident access for batched drivers: the engine's own device buffer for a field
  * ("x0", "yref", "x", "u", "status", "qp_iter"), element type double (NMPC_FP64) or float
- * (NMPC_FP32) / int32. Writing "x0"/"yref" there before nmpc_solve_async() skips the copy. */
+ * (NMPC_FP32) / int32. Writing "x0"/"yref" there before nmpc_solve_async() skips the copy.
+ * The solution sensitivities' buffers (fp64 handles; allocated at the first request or nmpc_sens_* call, so the first
+ * one waits for the device): "sens_x" batch*nx*nx, "sens_u" batch*nu*nx, "sens_status" batch int32, the cotangents
+ * "seed_x" batch*(N+1)*nx and "seed_u" batch*N*nu (zero until written), "grad_x0" batch*nx, "grad_yref"
+ * batch*(N*ny+ny_e). */
 int nmpc_device_ptr(nmpc_solver *h, const char *field, void **out);
 
 /* solve all instances. nmpc_solve: upload host-staged inputs, launch, wait, download; returns
@@ -327,6 +333,40 @@ int nmpc_closed_loop_get_history_int(nmpc_solver *h, const char *field, int inst
  * fixed (no floating-point atomics): two calls return the same bits. Waits for the stream. */
 int nmpc_closed_loop_history_envelope(nmpc_solver *h, int step0, int nsteps,
                                       double *out, size_t count);
+
+/* ------------------------------------------------------------------ solution sensitivities
+ * How the solution moves with its inputs, on the region where its active set S holds (fp64 handles of the lean
+ * loop's shapes nx/nu = 4/2, 6/2, 13/4, any horizon with (N+1)(nx+nu) <= 576). With z = z_0 + W[:,S] nu the
+ * solution at S (z_0 = T_x x0bar + V_y yref + const the unconstrained one, W the projected inverse Hessian):
+ *   forward   dz/dx0bar = T_x - W[:,S] W_SS^-1 T_x[S,:]      (acados: eval_solution_sensitivity(stage, "initial_state");
+ *             row block u_0 is the feedback gain K_0 = du_0/dx0bar of the advanced-step update u = u_0 + K_0 (x_meas - x0bar))
+ *   adjoint   J'g for a cotangent g on (x, u):  g~ = g - E_S' W_SS^-1 (W[S,:] g);  grad_x0 = T_x' g~;  grad_yref = V_y' g~
+ * One wavefront per instance (nmpc_sens.hip): S is read off the stored solution (z within 1e-7 (1 + |b|) of a bound;
+ * x_0 is pinned and never a member), W_SS is factored by Cholesky in LDS, every sum has a fixed order: two calls
+ * return the same bits. Per-instance status ("sens_status"): */
+#define NMPC_SENS_OK 0
+#define NMPC_SENS_DEGENERATE 1     /* a dependent active bound was dropped: one-sided derivative */
+#define NMPC_SENS_NO_SOLUTION 2    /* the instance's solve status != 0: outputs NaN */
+#define NMPC_SENS_SET_TOO_LARGE 3  /* more than 64 active bounds: outputs NaN */
+/* Which solution is differentiated: the one in the handle's device outputs — after nmpc_solve / nmpc_solve_async
+ * (in stream order: the _async forms enqueue behind the solve and never wait on the host, except the very first call's
+ * allocation), or the last step's solution after a lean-loop run with nmpc_closed_loop_set_outputs on; otherwise
+ * NMPC_ESTATE. The calls never change x / u / status / qp_iter.
+ * Errors: NMPC_EINVAL for a stage outside [0, N] or a wrong count; NMPC_EUNSUPPORTED (with a message) for fp32
+ * handles, shapes without the kernel, and handles without the unconstrained tables (condensed family, finish off).
+ * The synchronous forms wait for the stream and return the largest per-instance status (>= 0) or an error (< 0).
+ *
+ * d x_stage / d x0bar -> sens_x [batch][nx][nx];  d u_stage / d x0bar -> sens_u [batch][nu][nx]
+ * (device fields "sens_x" / "sens_u"). Either output may be NULL with count 0; at stage == N there is no u:
+ * sens_u must be NULL, else NMPC_EINVAL. */
+int nmpc_sens_forward_async(nmpc_solver *h, int stage);
+int nmpc_sens_forward(nmpc_solver *h, int stage, double *sens_x, size_t count_x, double *sens_u, size_t count_u);
+/* cotangents in the layouts of get_batch "x" / "u" (a NULL one is zero; count 0); grad_x0 [batch][nx],
+ * grad_yref [batch][N*ny+ny_e] (either may be NULL with count 0). The _async form reads the device cotangents
+ * "seed_x" / "seed_u" as they are and writes "grad_x0" / "grad_yref". V_y is built at the first adjoint call. */
+int nmpc_sens_adjoint_async(nmpc_solver *h);
+int nmpc_sens_adjoint(nmpc_solver *h, const double *gx, size_t cgx, const double *gu, size_t cgu,
+                      double *grad_x0, size_t c0, double *grad_yref, size_t cy);
 
 /* plant simulator (AcadosSimSolver for src/plant.py:27-43): one step of the nonlinear 2-D
  * Crazyflie plant x=[px,pz,vx,vz], u=[theta, F_d] on the device for `batch` states.
