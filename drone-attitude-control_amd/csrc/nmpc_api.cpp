@@ -1574,6 +1574,15 @@ int nmpc_sim_plant(int device, int batch, int num_stages, double T, double mass,
 
 namespace {
 
+// env NMPC_CLF_SMALLSET=0: the active-set rounds of the lean kernels and the solve finishes take the general set
+// solve for every set size (A/B and test switch; default: sets of one bound take the one-fetch step,
+// nmpc_cl_fast.hip solve_set_one)
+int clf_smallset()
+{
+    const char *ss = std::getenv("NMPC_CLF_SMALLSET");
+    return (ss && ss[0] == '0') ? 0 : 1;
+}
+
 template <typename T>
 nmpc::ClParams<T> cl_params(nmpc_solver *h)
 {
@@ -1818,6 +1827,7 @@ hipError_t fin32_enqueue(nmpc_solver *h)
     p.nslot = h->fin_nslot;
     p.polish_steps = h->polish_steps;
     p.gi = 1;
+    p.smallset = clf_smallset();
     p.s_lb = h->d_fin_f + h->fino[0];
     p.s_ub = h->d_fin_f + h->fino[1];
     p.uinit = h->d_fin_f + h->fino[2];
@@ -2009,6 +2019,7 @@ int sf_enqueue(nmpc_solver *h, hipEvent_t e0, hipEvent_t e1)
     // env NMPC_CLF_NO_GI=1 (test knob): no dual fallback, so unsettled instances park and take the full solve
     const char *nogi = std::getenv("NMPC_CLF_NO_GI");
     p.gi = (nogi && nogi[0] == '1') ? 0 : 1;
+    p.smallset = clf_smallset();
     p.s_lb = h->d_f64 + h->f64o[0];
     p.s_ub = h->d_f64 + h->f64o[1];
     p.uinit = h->d_f64 + h->f64o[2];
@@ -2344,6 +2355,7 @@ nmpc::ClFastParams<T> clf_params(nmpc_solver *h, int target, int step0, int nois
     // not settle parks and takes the list-mode full solve (tests/test_gpu_bench_parity.py forces parks)
     const char *nogi = std::getenv("NMPC_CLF_NO_GI");
     p.gi = (nogi && nogi[0] == '1') ? 0 : 1;
+    p.smallset = clf_smallset();
     const char *lw = std::getenv("NMPC_LOCK_WORKERS");
     // wavefronts per workgroup that start in phase 2 (drain demoted instances while the others still run
     // lockstep). Round 4: quad13 B = 8192 415M (0) -> 458-463M (1), 452-457M (2), 405-412M (3) steps/s

@@ -385,6 +385,8 @@ __device__ T init_point(const ClFastParams<T> &p, int nx, int nz, int k, int r, 
 // readlane, every other row eliminates column c, so at the end nu_i = t_i / (row i's pivot). Pivots get
 // fast_finish's regularisation (below 1e-9 of W_ii: + 1e-6 W_ii), i.e. the same regularised system the
 // oracle's Cholesky solves. The diagonal W_ii goes to L.wdg (the multiplier test). pd: every W_ii > 0.
+// Serves the sets of 2..16 bounds (and those of one bound with the small-set step switched off or on the
+// two- and five-slot shapes: solve_set_one repeats this elimination's pivot 0 operation for operation).
 template <typename T, int WSM, int EPL, class LdsT>
 __device__ double solve_set_gj(const ClFastParams<T> &p, LdsT &L, const SlotView<EPL> &sv, int m, int lane, double t, bool &pd)
 {
@@ -754,6 +756,46 @@ __device__ int load_set(LdsT &L, const SlotView<EPL> sv, int lane, unsigned wf, 
     return m;
 }
 
+// The active-set step of a set of one bound (SM = 1; 95 % of the quad13 loop's non-empty set steps, DESIGN.md
+// §3.12) with one fetch of W: the row W[e_0][:] at the lane's slots — the words w_combo_slots loads
+// for this set — in flight together. W_SS is one word of that row: the lane that holds the bound's slot has
+// W[e_0][e_0] in w[j], the word solve_set_gj's lane 0 gathers, and every lane takes it by readlane. Then
+// solve_set_gj's pivot 0 on every lane: the same regularisation and the final t / d (the pivot's own row takes
+// its update with f = 0), so nu is the general path's to the bit, without the W_SS gather's dependent round
+// trip, the 16 unrolled pivot blocks and the combination's second fetch. w: the row, kept for the combination;
+// returns nu (wave-uniform) and writes W_00 to L.wdg as solve_set_gj does.
+// Sets of 2..4 stay on the general path: holding their rows beside the block and its right-hand sides spills in
+// the kernels at their register limit (quad13 lockstep: 4 -> 10 VGPRs with two rows, 54 with four) and costs
+// the solve finishes a wavefront per SIMD; so do the five-slot shapes (jerk) with one row. The two-slot shapes
+// (force N = 20) keep the general path too: their one-wavefront-per-SIMD variant, already on AGPRs, measured
+// 4.5 % slower at B = 1024 with the row held (SMALL_SET<EPL>)
+constexpr int SM = 1;
+template <int EPL>
+constexpr bool SMALL_SET = EPL == 3 || EPL == 4;
+template <typename T, int EPL, class LdsT>
+__device__ __forceinline__ double solve_set_one(const ClFastParams<T> &p, LdsT &L, const SlotView<EPL> &sv, int lane,
+                                                double (&w)[EPL], bool &pd)
+{
+    const int row = L.se_e[0], rs = L.gi_slot[0];
+#pragma unroll
+    for (int j = 0; j < EPL; j++) {
+        const int e = sv.e(j);
+        w[j] = e >= 0 ? sv.w(p, row, rs, e, j * 64 + sv.lane) : 0.0;
+    }
+    // the bound's slot rs = j * 64 + lane (wave-uniform): its holder's w[j]
+    const int hs = __builtin_amdgcn_readfirstlane(rs);
+    double wh = w[0];
+#pragma unroll
+    for (int j = 1; j < EPL; j++)
+        if ((hs >> 6) == j) wh = w[j];
+    const double wcc = bcast(wh, hs & 63);
+    if (lane == 0) L.wdg[0] = wcc;
+    pd = wcc > 0.0;
+    const double d = wcc > 1e-9 * wcc ? wcc : fmax(wcc, 0.0) + 1e-6 * wcc;
+    const double t = L.se_t[0];
+    return fma(-0.0, t, t) / d;   // (the pivot row's own update: f = 0)
+}
+
 // Primal-dual active-set steps on W (oracle/c/riccati_ipm.c fast_finish): wf holds the set (warm
 // start, or empty: the first set from z_0's violations — the violated inputs and each state
 // component's most violated stage), z z_0 at the lane's slots. Each round solves W_SS nu = b_S - z_0,S: W_SS gathered
@@ -765,11 +807,14 @@ __device__ int load_set(LdsT &L, const SlotView<EPL> sv, int lane, unsigned wf, 
 // finish's PDAS rule. An emptied set restarts from z_0 (one round). Result: ok | m << 8 | steps << 16
 // (z in L.zb, the set in L.se_*); not ok: a set larger than WSM, W_SS not positive definite, or no
 // acceptance in polish_steps rounds. z: z_0 in, the solution out (when accepted); wf: the set the rounds start from
-// in, the set they reached out (the dual fallback starts from it)
+// in, the set they reached out (the dual fallback starts from it).
+// A round's set solve and combination by set size m: 1 solve_set_one (one W fetch for both; shapes of three or
+// four slots per lane); 2..16 solve_set_gj + w_combo_slots; 17..WSM (the force shape) sweep_inverse + h_matvec +
+// w_combo_slots.
 template <int WSM, int EPL>
 using WCacheOf = WCache<WSM + 1, EPL * 64>;
 
-template <typename T, int NX, int NU, int EPL, int WSM, class LdsT>
+template <typename T, int NX, int NU, int EPL, int WSM, bool SMALL = true, class LdsT>
 __device__ int wsteps_run(const ClFastParams<T> &p, LdsT &L, const SlotView<EPL> sv, int lane, T (&z)[EPL], unsigned &wf,
                           int rounds, WCacheOf<WSM, EPL> *wc = nullptr)
 {
@@ -862,10 +907,18 @@ __device__ int wsteps_run(const ClFastParams<T> &p, LdsT &L, const SlotView<EPL>
         // nu = W_SS^-1 (b - z_0)_S, lane i holding row i: Gauss-Jordan in registers for sets of up to 16
         // (one lane per row) and 32 (two lanes per row: register rows of 32 would go to scratch), the LDS
         // Cholesky beyond
+        // A set of one bound (p.smallset; env NMPC_CLF_SMALLSET=0: off) takes solve_set_one: one fetch of W[e_0, :]
+        // serves the set solve and the combination. Larger sets keep the paths below; a chain of rounds may cross
+        // the limit in both directions
         bool pd = true;
         double y;
+        double w1[EPL], nu1 = 0.0;
+        const bool small = SMALL && SMALL_SET<EPL> && p.smallset && m <= SM && !(NMPC_WCACHE && sv.wc_);
         CLF_T(ts0);
-        if (WSM <= 16 || m <= 16) {
+        if (small) {
+            nu1 = solve_set_one<T, EPL>(p, L, sv, lane, w1, pd);
+            y = lane == 0 ? nu1 : 0.0;
+        } else if (WSM <= 16 || m <= 16) {
             y = solve_set_gj<T, (WSM < 16 ? WSM : 16)>(p, L, sv, m, lane, lane < m ? L.se_t[lane] : 0.0, pd);
         } else {
             // sets of 17..WSM: the sweep's explicit inverse, nu = H (b - z_0)_S
@@ -902,7 +955,13 @@ __device__ int wsteps_run(const ClFastParams<T> &p, LdsT &L, const SlotView<EPL>
 #pragma unroll
         for (int j = 0; j < EPL; j++) zd[j] = (double)z0[j];
         CLF_T(tc0);
-        w_combo_slots<T, EPL>(p, L.se_e, L.gi_slot, sv, L.se_nu, m, zd);
+        if (small) {   // the row solve_set_one holds
+#pragma unroll
+            for (int j = 0; j < EPL; j++)
+                if (sv.e(j) >= 0) zd[j] = fma(w1[j], nu1, zd[j]);
+        } else {
+            w_combo_slots<T, EPL>(p, L.se_e, L.gi_slot, sv, L.se_nu, m, zd);
+        }
         CLF_TADD(L, 4, tc0);
         CLF_T(tk0);
 #pragma unroll
@@ -1363,7 +1422,7 @@ __device__ void write_outputs(const ClFastParams<T> &p, LdsT &L, const SlotView<
 // fallback (gi_prev: saturation arcs, where the shifted set is right or the fallback is needed again) —
 // the run after the fallback polish_steps. z: z_0 in, the solution out when accepted. Returns status |
 // accepted << 8 | ran the fallback << 9 | set size << 10 | (status 4 ? 0 : 1 + active-set steps) << 18.
-template <typename T, int NX, int NU, int EPL, int WSM, class LdsT>
+template <typename T, int NX, int NU, int EPL, int WSM, bool SMALL = true, class LdsT>
 __device__ int slow_step(const ClFastParams<T> &p, LdsT &L, const SlotView<EPL> sv0, int lane, const double *abl,
                          const double *cl, T (&z)[EPL], unsigned wf, bool cert_first, bool gi_prev,
                          WCacheOf<WSM, EPL> *wc = nullptr)
@@ -1391,7 +1450,7 @@ __device__ int slow_step(const ClFastParams<T> &p, LdsT &L, const SlotView<EPL> 
     for (int pass = 0; pass < 2 && status != 4; pass++) {
         const int rounds = pass == 1 ? p.polish_steps : (gi_prev ? 1 : min(p.polish_steps, PDAS_ROUNDS));
         CLF_T(tw0);
-        r = wsteps_run<T, NX, NU, EPL, WSM>(p, L, sv, lane, z, wset, rounds, wc);
+        r = wsteps_run<T, NX, NU, EPL, WSM, SMALL>(p, L, sv, lane, z, wset, rounds, wc);
         CLF_TADD(L, 2, tw0);
         steps_ += r >> 16;
         if ((r & 1) || pass == 1) break;
@@ -1954,7 +2013,8 @@ __global__ __launch_bounds__(64 * WPB) void fin32_kernel(ClFastParams<float> p)
             ok = !__any(bad);
         }
         if (!ok) {
-            const int sr = slow_step<T, NX, NU, EPL, WSM>(p, L, sv, lane, abl, cl, z, wf, false, false);
+            // (the general set solve for every size: the quad13 instantiation sits at 168 VGPRs, three wavefronts per SIMD)
+            const int sr = slow_step<T, NX, NU, EPL, WSM, false>(p, L, sv, lane, abl, cl, z, wf, false, false);
             ok = ((sr >> 8) & 1) && (sr & 0xff) == 0;
             m_acc = (sr >> 10) & 0xff;
             steps = sr >> 18;

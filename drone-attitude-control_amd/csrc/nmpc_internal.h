@@ -140,6 +140,8 @@ struct ClFastParams {
     int lock_direct;              // lockstep kernel: the leading claim-order groups straight to the phase-2 queue (1: warm-started)
     int claim_global;             // cl_fast_kernel: instances from one device-wide counter (park_count[1])
     int wcache;                   // 1: the rare path's W column cache in LDS (quad13 / jerk shapes; env NMPC_CLF_WCACHE=0: off)
+    int smallset;                 // 1: active-set rounds of one bound take the one-fetch step (solve_set_one; env
+                                  // NMPC_CLF_SMALLSET=0: the general path for every size)
     const int *gorder;            // or null: claim position -> instance of the device-wide claim (clf_order_launch)
     const int *inst_map;          // or null: position -> instance of the per-workgroup claim ranges (nmpc_api.cpp
                                   // clf_xcd_map: each XCD's workgroups own a contiguous stretch of reference-table rows)
